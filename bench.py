@@ -2,14 +2,22 @@
 """Throughput benchmark of the MI355X F-16 environment (BASELINE.json configs[2]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--stack 4]
+                    [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one process per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the line with the headline, the
+roofline on the timed region's own time and the episode mix. --full adds everything measured
+beside it, each in runs of its own after the timed region: the step kernel's per-launch
+duration for the roofline, the contiguous layout (`layouts`), the features / telemetry /
+sampler / rollout / cfg1 / cfg2 / SB3 legs and the CPU baseline. --dump-outputs DIR writes the
+StepOut of the last timed step as DIR/<field>.npy (dump_outputs).
 
 A "step" is one VecEnv step (4 FDM frames + obs/reward/termination/auto-reset) of every env
 on the GPU, driven through the device-tensor VecEnv boundary (F16Envs.step) with random
 actions from the device Philox stream, pre-generated into HBM before the timed region.
 The observation layout is the windowed one (F16Envs(obs_layout="window"): the (N, K, 15)
 obs is a strided view of per-env frame histories, one new 64-B frame slot written per step);
-the contiguous ping-pong layout is timed beside it (`layouts`).
+with --full the contiguous ping-pong layout is timed beside it (`layouts`).
 Envs shard across ranks (weak scaling, no collective in the stepping loop); the job-level
 value is all ranks' env-steps divided by the max-over-ranks wall time.
 
@@ -18,7 +26,7 @@ Prints ONE JSON line on rank 0 (driver contract), including
                   must move; SURVEY 8(d)'s B(K) beside it as contract_*) / its average launch
                   duration (HIP events on the launch stream), vs the 8 TB/s HBM peak;
                   `traffic` = PMC-measured HBM bytes per launch from profiles/ if present;
-  cpu_baseline -- the CPU oracle (oracle/f16ref.c, fp64 C restatement, OpenMP) timed on this
+  cpu_baseline -- (--full) the CPU oracle (oracle/f16ref.c, fp64 C restatement, OpenMP) timed on this
                   host on a bounded sample of the same workload (rank 0, at every N, after the
                   closing barrier); rccl_world -- the size of the group RCCL reports.
 """
@@ -52,9 +60,14 @@ def parse():
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (cfg3 65536, cfg5 131072)")
     ap.add_argument("--stack", type=int, default=4)
     ap.add_argument("--obs-layout", choices=("window", "contiguous"), default="window",
-                    help="observation layout of the headline (the other is timed beside it at N=1)")
+                    help="observation layout of the headline (--full times the other beside it at N=1)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample budget")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything measured beside it: the step kernel's own "
+                         "duration (roofline), the side legs, the other layout, the rollout and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the StepOut fields) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample budget (--full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
                     help="N > 1 process group: nccl (RCCL over xGMI, the measurement); gloo only "
@@ -138,13 +151,13 @@ def closing_fields(args, world, n, stack, cfg5=False, leg=None):
     """The fields every result line carries at every N, made on rank 0 after
     the closing barrier, when no rank is timing anything: the process group as the collective
     library reports it (`rccl_world`: dist.get_world_size() of the nccl = RCCL group; None under
-    gloo or without a group) and the CPU baseline."""
+    gloo or without a group) and, with --full, the CPU baseline."""
     import torch.distributed as dist
     pg = {"backend": None, "world_size": 1}
     if dist.is_available() and dist.is_initialized():
         pg = {"backend": str(dist.get_backend()), "world_size": dist.get_world_size()}
     out = {"process_group": pg, "rccl_world": pg["world_size"] if pg["backend"] == "nccl" else None}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         run = leg or (lambda name, fn, *a: fn(*a))
         out["cpu_baseline"] = run("cpu_baseline", cpu_baseline, n, stack, args.cpu_seconds, cfg5)
     return out
@@ -973,6 +986,33 @@ def load_valu(envs, stack, kernel):
     return None
 
 
+DUMP_BUDGET = 64 * 10 ** 6  # bytes: all the arrays of one dump together
+
+
+def dump_outputs(path, out, rank, seed):
+    """--dump-outputs: the StepOut the last timed step returned -- what a caller of F16Envs.step
+    holds after it -- as `path`/<field>.npy (rank r > 0: <field>.rank<r>.npy), float64 for
+    ep_return, float32 for the rest. A dump over DUMP_BUDGET keeps a fixed, seeded sample of the
+    envs instead: the same rows of every array, their indices in env_index.npy."""
+    import numpy as np
+    import torch
+    n = out.obs.shape[0]
+    wide = {k: torch.float64 if v.dtype == torch.float64 else torch.float32 for k, v in out._asdict().items()}
+    per_env = sum(v[0].numel() * (8 if wide[k] == torch.float64 else 4) for k, v in out._asdict().items())
+    idx = None
+    if n * per_env > DUMP_BUDGET:
+        m = DUMP_BUDGET // (per_env + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+    os.makedirs(path, exist_ok=True)
+    sfx = ".npy" if rank == 0 else ".rank%d.npy" % rank
+    sel = None if idx is None else torch.as_tensor(idx, device=out.obs.device)
+    for k, v in out._asdict().items():
+        a = v if sel is None else v.index_select(0, sel)
+        np.save(os.path.join(path, k + sfx), np.ascontiguousarray(a.to(wide[k]).cpu().numpy()))
+    if idx is not None:
+        np.save(os.path.join(path, "env_index" + sfx), idx.astype(np.float64))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ:
@@ -1058,8 +1098,9 @@ def main():
     gc.disable()  # no collector pause inside the timed steps (a gc.collect() here idles the GPU ~50 ms)
     t0 = time.perf_counter()
     start_ev.record(stream)
+    last = None
     for t in range(args.steps):
-        envs.step(act_views[t % pool])
+        last = envs.step(act_views[t % pool])
     end_ev.record(stream)
     torch.cuda.synchronize()
     # each rank's own K steps, barrier to barrier; the job's time is the max over ranks (all_reduce
@@ -1073,17 +1114,8 @@ def main():
     # auto-resets inside the timed region, from the lanes' episode counters (read after it:
     # nothing is added to the timed loop)
     resets_timed = int((envs.get_state()[:, F16C_EP_COUNT].sum() - ep0).item())
-    # per-launch duration of the step kernel: start/stop events recorded by each launch's own
-    # dispatch packet (hipExtLaunchKernel, f16env_profile_*) on the launch stream, over a
-    # second pass of the same steps -- the kernel's execution, as rocprofv3's kernel trace
-    # measures it, without the dependent-launch boundary the timed region above includes
-    nk = max(200, min(args.steps, 500))  # >= 200 launches: a 20-step run's mean is one outlier away from noise
-
-    def second_pass():
-        for t in range(nk):
-            envs.step(acts[t % pool])
-
-    kern_ms, kern_min_ms, _ = envs.profile_kernel(second_pass, nk)
+    if args.dump_outputs and last is not None:  # before anything steps these envs again
+        dump_outputs(args.dump_outputs, last, rank, args.seed)
     legs_failed = []
 
     def leg(name, fn, *a, **kw):
@@ -1099,24 +1131,39 @@ def main():
             legs_failed.append(name)
             return {"error": "%s: %s" % (type(ex).__name__, ex)}
 
-    feat = leg("features", features_bench, envs, stream)
-    telem = leg("telemetry", telemetry_bench, envs, stream)
-    sampler = leg("sampler", sampler_bench, envs, stream)
+    # A plain run stops measuring here; everything below that launches a kernel is --full's.
+    kern_ms = kern_min_ms = 0.0
+    feat = telem = sampler = None
+    if args.full:
+        # per-launch duration of the step kernel: start/stop events recorded by each launch's own
+        # dispatch packet (hipExtLaunchKernel, f16env_profile_*) on the launch stream, over a
+        # second pass of the same steps -- the kernel's execution, as rocprofv3's kernel trace
+        # measures it, without the dependent-launch boundary the timed region above includes
+        nk = max(200, min(args.steps, 500))  # >= 200 launches: a 20-step run's mean is one outlier away from noise
+
+        def second_pass():
+            for t in range(nk):
+                envs.step(acts[t % pool])
+
+        kern_ms, kern_min_ms, _ = envs.profile_kernel(second_pass, nk)
+        feat = leg("features", features_bench, envs, stream)
+        telem = leg("telemetry", telemetry_bench, envs, stream)
+        sampler = leg("sampler", sampler_bench, envs, stream)
     if world > 1:
         tt = torch.tensor([elapsed, kern_ms, gpu_ms_per_step, kern_min_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, kern_ms, gpu_ms_per_step, kern_min_ms = float(tt[0]), float(tt[1]), float(tt[2]), float(tt[3])
     venv.close()
-    del acts, warm
+    del acts, warm, last
     torch.cuda.empty_cache()
-    one = world == 1 and not cfg5
+    one = args.full and world == 1 and not cfg5
     sb3 = leg("sb3_compat", sb3_compat_bench, dev, n) if (one and not args.no_cpu_baseline) else None
     cfg2 = leg("cfg2", cfg2_bench, dev) if (one and not args.no_cpu_baseline) else None
     persist = leg("persistent", persistent_bench, dev, n, args.stack, 1000, args.seed + 6000) if one else None
     other = "contiguous" if args.obs_layout == "window" else "window"
     layouts = leg("layouts", layout_leg, dev, args, other) if one else None
     rollout = None
-    if not cfg5 and args.rollout_envs > 0 and args.rollout_steps > 0:
+    if args.full and not cfg5 and args.rollout_envs > 0 and args.rollout_steps > 0:
         rollout = leg("rollout", rollout_bench, args, dev, rank, world)
     cfg1 = leg("cfg1_hip", cfg1_hip_bench, dev) if one else None
 
@@ -1143,8 +1190,10 @@ def main():
     # launch duration used for the roofline: the kernel's average execution time from its own
     # dispatch events (what rocprofv3 --kernel-trace reports); the timed region's GPU time per
     # launch (back-to-back launches incl. the ~1.5 us dependent-kernel boundary) beside it
-    # (cfg5: the step is two kernels -- step + deferred reset -- so the region time is used)
-    roof_ms = gpu_ms_per_step if cfg5 else kern_ms
+    # (cfg5: the step is two kernels -- step + deferred reset -- so the region time is used; a
+    # plain run makes no second pass and quotes the region time too)
+    region_roof = cfg5 or not args.full
+    roof_ms = gpu_ms_per_step if region_roof else kern_ms
     achieved = bytes_per_launch / (roof_ms * 1e-3) / 1e9
     traffic = load_traffic(n, args.stack, envs.state_bytes_per_env, args.obs_layout,
                            "pmc_traffic_cfg5.json" if cfg5 else "pmc_traffic.json")
@@ -1155,6 +1204,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 5),
         "higher_is_better": True,
         "scaling": "weak",
@@ -1193,9 +1243,10 @@ def main():
             "kernel": kernel_name + (" + f16_ic_fill_kernel (reset cache refill)" if cfg5 else ""),
             "waves_per_simd": waves_per_simd,
             "kernel_ms": round(roof_ms, 5),
-            "kernel_ms_min": round(kern_min_ms, 5),
+            "kernel_ms_min": round(kern_min_ms, 5) if args.full else None,
             "kernel_timing": ("HIP events around the timed region / launches (step kernels + the amortised reset-cache refills)" if cfg5 else
-                              "start/stop HIP events recorded by each launch's dispatch packet (hipExtLaunchKernel) "
+                              "HIP events around the timed region / launches (--full: each launch's own dispatch events)"
+                              if region_roof else "start/stop HIP events recorded by each launch's dispatch packet (hipExtLaunchKernel) "
                               "on the launch stream, mean over %d launches" % nk),
             "region_ms_per_launch": round(gpu_ms_per_step, 5),
             "region_timing": "HIP events around the timed region on the launch stream / launches",
@@ -1216,10 +1267,9 @@ def main():
             "setup": burn,
             "source": "sum of the lanes' episode counters after minus before the timed region / (envs x steps)",
         },
-        "features": feat,
-        "telemetry": telem,
-        "sampler": sampler,
     }
+    if args.full:
+        out.update({"features": feat, "telemetry": telem, "sampler": sampler})
     if rollout is not None:
         out["rollout"] = rollout
     if sb3 is not None:

@@ -20,7 +20,7 @@ def _run(args, env=None, timeout=240):
 
 
 def test_gpus2_spawns_two_ranks_and_relays_rank0_line():
-    p = _run(["--gpus", "2", "--launch-selftest", "--cpu-seconds", "0.3"])
+    p = _run(["--gpus", "2", "--launch-selftest", "--full", "--cpu-seconds", "0.3"])  # --full: the CPU baseline
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout  # exactly the relayed line on stdout

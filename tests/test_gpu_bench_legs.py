@@ -37,8 +37,34 @@ def _bench(extra, timeout=900):
 
 
 @pytest.mark.gpu
+def test_plain_run_has_the_headline_only_and_dumps_its_last_step(gpu, tmp_path):
+    """Without --full the line carries the headline and none of the side legs (--fail-leg finds no
+    leg to fail); --dump-outputs writes the StepOut of the last timed step, the same from run to run."""
+    dumps = []
+    for name in ("a", "b"):
+        p, d = _bench(["--fail-leg", "rollout", "--dump-outputs", str(tmp_path / name)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert d["full"] is False and d["steps"] == 5 and d["warmup"] == 2
+        assert d["value"] > 0 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(4096 / (d["ms_per_step"] * 1e-3), rel=1e-2)
+        assert d["legs_failed"] == []
+        for k in ("features", "telemetry", "sampler", "rollout", "sb3_compat", "cfg2", "persistent_random_policy",
+                  "cfg1_hip", "layouts", "cpu_baseline"):
+            assert k not in d, k
+        dumps.append({f: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = dumps
+    assert sorted(a) == [f + ".npy" for f in ("ep_len", "ep_return", "obs", "rew", "terminal_obs", "terminated",
+                                              "truncated")]
+    assert a["obs.npy"].shape == a["terminal_obs.npy"].shape == (4096, 4, 15) and a["obs.npy"].dtype == np.float32
+    assert a["ep_return.npy"].dtype == np.float64 and a["rew.npy"].shape == (4096,)
+    assert np.isfinite(a["obs.npy"]).all() and np.any(a["obs.npy"] != 0) and np.any(a["rew.npy"] != 0)
+    for f in a:
+        np.testing.assert_array_equal(a[f], b[f], err_msg=f)
+
+
+@pytest.mark.gpu
 def test_forced_leg_failure_exits_nonzero(gpu):
-    p, d = _bench(["--fail-leg", "rollout"])
+    p, d = _bench(["--full", "--fail-leg", "rollout"])  # --full: the side legs run only there
     assert p.returncode == 1, p.stderr[-3000:]
     assert d is not None, "the headline line must still be printed"
     assert d["legs_failed"] == ["rollout"]

@@ -8,7 +8,6 @@ import json
 import math
 import os
 import re
-import xml.etree.ElementTree as ET
 
 import numpy as np
 import pytest
@@ -17,7 +16,6 @@ from oracle_ref import OracleEnvs, atmosphere, default_ic, lib, philox
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-REF_XML = "/root/reference/aircraft/f16/f16.xml"
 
 
 def model():
@@ -28,25 +26,22 @@ def model():
 # ------------------------------------------------------------------------------------------
 # tables: fixture vs XML (when the reference is present) and oracle lookups vs fixture
 # ------------------------------------------------------------------------------------------
-@pytest.mark.skipif(not os.path.exists(REF_XML), reason="reference XML not present")
 def test_fixture_matches_reference_xml():
+    """f16_model.json against the reference XML's own text, as recorded in f16_xml_tables.json
+    (tests/golden/make_f16_xml_tables.py: names, lines, property names, table data as strings)."""
     m = model()
-    root = ET.parse(REF_XML).getroot()
-    aero = root.find("aerodynamics")
-    by_name = {}
-    for axis in aero.findall("axis"):
-        for f in axis.findall("function"):
-            by_name[f.get("name").split("/")[-1]] = f
+    with open(os.path.join(GOLD, "f16_xml_tables.json")) as f:
+        by_name = {x["name"].split("/")[-1]: x for x in json.load(f)["functions"]}
     assert len(by_name) == len(m["aero_functions"]) == 40
     for fn in m["aero_functions"]:
         x = by_name[fn["name"]]
-        props = [p.text.strip() for p in x.find("product").findall("property")]
+        props = [p.strip() for p in x["props"]]
         assert props == fn["props"], fn["name"]
-        tab = x.find("product").find("table")
-        if tab is None:
-            assert float(x.find("product").find("value").text) == fn["value"]
+        assert x["line"] == fn["xml_line"] and fn["name"] in x["name"]
+        if "table_data" not in x:
+            assert float(x["value"]) == fn["value"]
             continue
-        toks = [ln.split() for ln in tab.find("tableData").text.strip().splitlines() if ln.strip()]
+        toks = [ln.split() for ln in x["table_data"].strip().splitlines() if ln.strip()]
         if fn["table"]["cols"] is None:
             assert [float(t[0]) for t in toks] == fn["table"]["rows"]
             assert [float(t[1]) for t in toks] == fn["table"]["data"]
@@ -54,9 +49,6 @@ def test_fixture_matches_reference_xml():
             assert [float(v) for v in toks[0]] == fn["table"]["cols"]
             assert [float(t[0]) for t in toks[1:]] == fn["table"]["rows"]
             assert [[float(v) for v in t[1:]] for t in toks[1:]] == fn["table"]["data"]
-        with open(REF_XML) as fh:
-            line = fh.read().splitlines()[fn["xml_line"] - 1]
-        assert fn["name"] in line
 
 
 def _kind_grid(t):

@@ -51,7 +51,7 @@ for s in $STEPS; do
     tests) run pytest_gpu_$TAG 1200 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
     prodtests) run pytest_prod 600 python -u -m pytest tests/test_gpu_production.py -m gpu -v -s --timeout 300 --timeout-method thread ;;
     smoke) run smoke_$TAG 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py --steps 1000 --warmup 50 ;;
+    bench) run bench 600 python bench.py --full --steps 1000 --warmup 50 ;;
     driver) run bench_driver_$TAG 600 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
     profdrv)  # rocprofv3 summary of the driver's exact command (the per-dispatch trace is dropped:
               # gpurun copies back at most 64 MiB of gpurun_out)
@@ -82,14 +82,14 @@ for s in $STEPS; do
       for P in ${ICC_PERIODS:-8 16 32 64 128}; do
         F16ENV_ICC_PERIOD=$P run bench_cfg5_icc${P}_$TAG 300 python bench.py --workload cfg5 --steps ${ICC_STEPS:-300} --warmup 20 --no-cpu-baseline
       done ;;
-    bench5) run bench_cfg5_$TAG 600 python bench.py --workload cfg5 --steps 300 --warmup 20 --cpu-seconds 5 ;;
+    bench5) run bench_cfg5_$TAG 600 python bench.py --full --workload cfg5 --steps 300 --warmup 20 --cpu-seconds 5 ;;
     variants) run variant_sweep 900 python tools/variant_sweep.py run --json "$OUT/variants_$TAG.json" ;;
     div) run cfg5_divergence_$TAG 900 python tests/cfg5_divergence.py --n 4096 --json "$OUT/cfg5_divergence_$TAG.json" ;;
     sweep) run kernel_sweep 600 python tools/kernel_sweep.py --json "$OUT/sweep_$TAG.json" ;;
     report) run parity_report 600 python tests/parity_report.py --n 256 --steps 300 --json "$OUT/parity_$TAG.json" ;;
     prof)
       run rocprof_stats 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$TAG" -o run --output-format csv -- \
-        python bench.py --steps 300 --warmup 20 --no-cpu-baseline --rollout-envs 0
+        python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --rollout-envs 0
       rm -f "$OUT/prof_$TAG/run_kernel_trace.csv" ;;
     sq)  # summarised on the box (pmc_valu_$TAG.json), the raw rows compressed
       run pmc_sq 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS -d "$OUT/pmc_sq_$TAG" -o run --output-format csv -- \
