@@ -294,33 +294,49 @@ __device__ __forceinline__ void st16(float4* p, float4 v) {
   }
 }
 
-template <bool GUST>
+// PART 0: every column. The step's counted-wait prologue unpacks in three parts, each where its
+// columns are first read (a part's few ALU operations -- the sign-flag masks, the recomputed
+// latch -- would otherwise wait for its columns where the whole unpack stands): 1 the columns the
+// Earth angle, the altitude reference and a frame's propagation read (C0-C9, C13, and the
+// recomputed latch); 2 C14, C15 and the wind columns (the FRESH flag, step and episode counts,
+// the gust update); 3 the FCS / engine columns C10-C12 (a frame reads them first in fcs_run).
+// L.flags: part 2 sets it to the FRESH bit, part 3 ors the augmentation bit in.
+template <bool GUST, int PART = 0>
 __device__ __forceinline__ void lane_unpack(const float4 (&c)[NCOL], float4 w, float4 g, Lane& L) {
-  L.rI[0] = f2d(c[0].x, c[0].y); L.rI[1] = f2d(c[0].z, c[0].w);
-  L.rI[2] = f2d(c[1].x, c[1].y); L.vI[0] = f2d(c[1].z, c[1].w);
-  L.vI[1] = f2d(c[2].x, c[2].y); L.vI[2] = f2d(c[2].z, c[2].w);
-  L.epa = f2d(c[3].x, c[3].y); L.ep_ret = f2d(c[3].z, c[3].w);
-  L.ndv1[0] = c[4].x; L.ndv1[1] = c[4].y; L.ndv1[2] = c[4].z; L.dv2[0] = c[4].w;
-  L.dv2[1] = c[5].x; L.dv2[2] = c[5].y; L.aI[0] = c[5].z; L.aI[1] = c[5].w;
-  L.aI[2] = c[6].x; L.aIp[0] = c[6].y; L.aIp[1] = c[6].z; L.aIp[2] = c[6].w;
-  L.q[0] = c[7].x; L.q[1] = c[7].y; L.q[2] = c[7].z; L.q[3] = c[7].w;
-  L.wI[0] = c[8].x; L.wI[1] = c[8].y; L.wI[2] = c[8].z; L.wId[0] = c[8].w;
-  L.wId[1] = c[9].x; L.wId[2] = c[9].y; L.ba[0] = 0.0f; L.ba[1] = c[9].z; L.ba[2] = c[9].w;
-  L.tef = c[10].x; L.ail = c[10].y; L.ele = c[10].z; L.rud = c[10].w;
-  L.lef = c[11].x; L.sb = c[11].y; L.pri = c[11].z; L.prp = c[11].w;
-  L.ppi = c[12].x; L.pyi = c[12].y; L.pyp = c[12].z; L.ppp = 0.0f;
-  L.n2 = without_sign_flag(c[12].w); L.n1 = 0.0f;
-  L.lx[F16L_ALPHA] = c[13].x; L.lx[F16L_BETA] = c[13].y; L.lx[F16L_MACH] = c[13].z; L.lx[F16L_VC_KTS] = c[13].w;
-  L.last_d = without_sign_flag(c[14].x); L.step = __float_as_int(c[14].y);
-  L.lx[F16L_NPY] = c[14].z; L.lx[F16L_NPZ] = c[14].w;
-  L.goal[0] = c[15].x; L.goal[1] = c[15].y; L.goal[2] = c[15].z; L.ep_count = __float_as_int(c[15].w);
-  L.flags = (sign_flag(c[12].w) ? LANE_FLAG_AUG : 0) | (sign_flag(c[14].x) ? LANE_FLAG_FRESH : 0);
-  latch_from_state(L);
+  if (PART == 0 || PART == 1) {
+    L.rI[0] = f2d(c[0].x, c[0].y); L.rI[1] = f2d(c[0].z, c[0].w);
+    L.rI[2] = f2d(c[1].x, c[1].y); L.vI[0] = f2d(c[1].z, c[1].w);
+    L.vI[1] = f2d(c[2].x, c[2].y); L.vI[2] = f2d(c[2].z, c[2].w);
+    L.epa = f2d(c[3].x, c[3].y); L.ep_ret = f2d(c[3].z, c[3].w);
+    L.ndv1[0] = c[4].x; L.ndv1[1] = c[4].y; L.ndv1[2] = c[4].z; L.dv2[0] = c[4].w;
+    L.dv2[1] = c[5].x; L.dv2[2] = c[5].y; L.aI[0] = c[5].z; L.aI[1] = c[5].w;
+    L.aI[2] = c[6].x; L.aIp[0] = c[6].y; L.aIp[1] = c[6].z; L.aIp[2] = c[6].w;
+    L.q[0] = c[7].x; L.q[1] = c[7].y; L.q[2] = c[7].z; L.q[3] = c[7].w;
+    L.wI[0] = c[8].x; L.wI[1] = c[8].y; L.wI[2] = c[8].z; L.wId[0] = c[8].w;
+    L.wId[1] = c[9].x; L.wId[2] = c[9].y; L.ba[0] = 0.0f; L.ba[1] = c[9].z; L.ba[2] = c[9].w;
+    L.lx[F16L_ALPHA] = c[13].x; L.lx[F16L_BETA] = c[13].y; L.lx[F16L_MACH] = c[13].z; L.lx[F16L_VC_KTS] = c[13].w;
+    latch_from_state(L);
+  }
+  if (PART == 0 || PART == 2) {
+    L.last_d = without_sign_flag(c[14].x); L.step = __float_as_int(c[14].y);
+    L.lx[F16L_NPY] = c[14].z; L.lx[F16L_NPZ] = c[14].w;
+    L.goal[0] = c[15].x; L.goal[1] = c[15].y; L.goal[2] = c[15].z; L.ep_count = __float_as_int(c[15].w);
+    L.flags = sign_flag(c[14].x) ? LANE_FLAG_FRESH : 0;
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    L.wst[j] = GUST ? (&w.x)[j] : 0.0f;
-    L.gust[j] = GUST ? (&g.x)[j] : 0.0f;
-    L.wind[j] = L.wst[j] + L.gust[j];
+    for (int j = 0; j < 3; ++j) {
+      L.wst[j] = GUST ? (&w.x)[j] : 0.0f;
+      L.gust[j] = GUST ? (&g.x)[j] : 0.0f;
+      L.wind[j] = L.wst[j] + L.gust[j];
+    }
+  }
+  if (PART == 0 || PART == 3) {
+    L.tef = c[10].x; L.ail = c[10].y; L.ele = c[10].z; L.rud = c[10].w;
+    L.lef = c[11].x; L.sb = c[11].y; L.pri = c[11].z; L.prp = c[11].w;
+    L.ppi = c[12].x; L.pyi = c[12].y; L.pyp = c[12].z; L.ppp = 0.0f;
+    L.n2 = without_sign_flag(c[12].w); L.n1 = 0.0f;
+    // (PART 0 keeps the one expression the unpack always had)
+    if (PART == 0) L.flags = (sign_flag(c[12].w) ? LANE_FLAG_AUG : 0) | (sign_flag(c[14].x) ? LANE_FLAG_FRESH : 0);
+    else L.flags |= sign_flag(c[12].w) ? LANE_FLAG_AUG : 0;
   }
 }
 // the lane's raw columns (and the wind columns of GUST handles), loads only: callers that want
@@ -337,6 +353,52 @@ __device__ __forceinline__ void lane_fetch(const SoA& s, int64_t k, float4 (&c)[
   if (GUST) {
     w = *p;
     g = *(p + n);
+  }
+}
+// The step prologue's issue order: the columns in the order of their first use in the step
+// (loads retire in issue order, so a counted s_waitcnt vmcnt(k) at a column's first use leaves
+// the k loads behind it in flight). The latch C13 feeds the frame's first instructions (the FCS
+// gain lookups); the recomputed latch, the Earth angle and the altitude reference read q / wI
+// (C7, C8), epa (C3) and rI / vI (C0-C2); the propagation the AB histories C4-C6 and C9; the
+// FRESH flag in C14 picks the fresh-frame DMA before the frames. Then the action (the caller's
+// load, between the two parts) and the FCS / engine columns C10-C12, which a frame first reads
+// after derive, the wind-axis block and the atmosphere. C15 (goal, episode count) is read by the
+// env layer after the frames and goes last -- except in builds that read it before them (C15_EARLY:
+// the wind kernels' gust draw is keyed by the episode count, and the 256-register windowed builds
+// stash it), where it follows C14, with the wind columns behind it.
+static constexpr int FETCH_ORDER[NCOL] = {13, 8, 7, 3, 0, 1, 2, 4, 5, 6, 9, 14, 10, 11, 12, 15};
+static constexpr int FETCH_SPLIT = 12;  // the action's load goes between [0, SPLIT) and [SPLIT, NCOL)
+constexpr bool fetch_order_is_permutation() {
+  int seen = 0;
+  for (int j = 0; j < NCOL; ++j) seen |= 1 << FETCH_ORDER[j];
+  return seen == (1 << NCOL) - 1 && FETCH_ORDER[NCOL - 1] == 15;
+}
+static_assert(fetch_order_is_permutation(), "FETCH_ORDER must name every column once, C15 last");
+// (the columns as 16-byte vectors in the global address space: global_load_dwordx4)
+typedef float v4f_t __attribute__((ext_vector_type(4)));
+typedef const v4f_t __attribute__((address_space(1))) * GCol;
+// one load, fenced: the scheduler may not reorder the loads among themselves (it clusters them
+// by address otherwise, and the order is what the counted waits rest on)
+__device__ __forceinline__ float4 fetch_col(GCol p) {
+  const float4 v = __builtin_bit_cast(float4, *p);
+  __builtin_amdgcn_sched_barrier(0);
+  return v;
+}
+// PART 0: the columns before the action's place (and the wind columns); 1: those after it
+template <bool GUST, bool C15_EARLY, int PART>
+__device__ __forceinline__ void lane_fetch_ordered(GCol cols, int64_t n, int64_t k, float4 (&c)[NCOL], float4& w, float4& g) {
+  const GCol p = cols + k;
+#pragma unroll
+  for (int i = PART ? FETCH_SPLIT : 0; i < (PART ? NCOL - (C15_EARLY ? 1 : 0) : FETCH_SPLIT); ++i)
+    c[FETCH_ORDER[i]] = fetch_col(p + FETCH_ORDER[i] * n);
+  if (PART == 0) {
+    if (C15_EARLY) c[15] = fetch_col(p + 15 * n);
+    w = make_float4(0.f, 0.f, 0.f, 0.f);
+    g = w;
+    if (GUST) {
+      w = fetch_col(p + COL_WIND * n);
+      g = fetch_col(p + COL_GUST * n);
+    }
   }
 }
 template <bool GUST = false>
@@ -429,6 +491,49 @@ __device__ __forceinline__ Seg bracket(const float (&bp)[N], const float* pairs,
   f = __builtin_amdgcn_fmed3f(f, 0.0f, 1.0f);
   return {i, f};
 }
+// Windowed bracket: the same segment and factor as bracket(), with the count shortened when
+// every active lane of the wave has x in (bp[KLO], bp[KHI]] (one wave-uniform test). There
+// bp[k] <= bp[KLO] < x for k <= KLO, so those interior breakpoints all count, and x <= bp[KHI]
+// <= bp[k] for k >= KHI, so none of those does; the sign-bit count runs over KLO < k < KHI only.
+// The windows are a tuning for where the workload flies, nothing depends on them:
+// a wave with a lane outside -- or a NaN / +-inf, which fails x > lo && x <= hi -- takes the
+// full count for all its lanes.
+constexpr int bracket_window_const(int n, int klo) {  // #{k in 1..n-2 : k <= klo}
+  return klo < n - 2 ? (klo > 0 ? klo : 0) : n - 2;
+}
+template <int KLO, int KHI, int N>
+__device__ __forceinline__ Seg bracket_window(const float (&bp)[N], const float* pairs, float x) {
+  // Off in the product: on the same-box A/B the windowed count was no faster than the full one
+  // (profiles/r07_ab_counted_waits.json). -DF16_BRACKET_WINDOW builds it;
+  // -DF16_BRACKET_FULL (the A/B reference's flag) always gives the full count.
+#if !defined(F16_BRACKET_WINDOW) || defined(F16_BRACKET_FULL)
+  return bracket(bp, pairs, x);
+#else
+  static_assert(0 <= KLO && KLO < KHI && KHI <= N - 1, "window ends must be breakpoints of the grid");
+  uint32_t c;
+  if (__ballot(!(x > bp[KLO] && x <= bp[KHI])) == 0) {
+    c = (uint32_t)bracket_window_const(N, KLO);
+#pragma unroll
+    for (int k = (KLO + 1 > 1 ? KLO + 1 : 1); k < (KHI < N - 1 ? KHI : N - 1); ++k) c += __float_as_uint(bp[k] - x) >> 31;
+  } else {
+    c = 0;
+#pragma unroll
+    for (int k = 1; k < N - 1; ++k) c += __float_as_uint(bp[k] - x) >> 31;
+  }
+  const int i = 1 + (int)c;
+  F16_CHECK(i >= 1 && i <= N - 1, DBG_TABLE_SEGMENT);
+  const float2 p = reinterpret_cast<const float2*>(pairs)[i - 1];
+  float f = (x - p.x) * p.y;
+  f = __builtin_amdgcn_fmed3f(f, 0.0f, 1.0f);
+  return {i, f};
+#endif
+}
+// the windows (indices into the grids; the static_asserts pin the values they stand for)
+enum { WIN_ALPHA_LO = 0, WIN_ALPHA_HI = 6, WIN_BETA_LO = 4, WIN_BETA_HI = 8, WIN_MACH_LO = 1, WIN_MACH_HI = 7 };
+static_assert(BP_alpha_bp[WIN_ALPHA_LO] == -0.175f && BP_alpha_bp[WIN_ALPHA_HI] == 0.349f, "alpha window (-10, 20] deg");
+static_assert(BP_beta13_bp[WIN_BETA_LO] == -0.175f && BP_beta13_bp[WIN_BETA_HI] == 0.175f, "beta window (-10, 10] deg");
+static_assert(BP_machu[WIN_MACH_LO] == 0.4f && BP_machu[WIN_MACH_HI] == 1.0f, "Mach window (0.4, 1.0]");
+
 // Guess-and-correct bracket (round 5): the same segment and factor as bracket(), from a guess
 // instead of a count. u(x) is a monotone map whose integer crossings b'_k (k = 1 .. N-3) lie
 // strictly inside segment k's span, bp[k] < b'_k <= bp[k+1]; the guess g = clamp(floor(u), 0,
@@ -1145,7 +1250,7 @@ __device__ __forceinline__ void aero(const AeroIn& a, const float* T, float* F6)
                 "guess-bracket crossings must lie inside their segments");
   const Seg sa = bracket_g_uniform(BP_alpha_bp, T + OFF_pair_alpha, a.alpha);
 #else
-  const Seg sa = bracket(BP_alpha_bp, T + OFF_pair_alpha, a.alpha);
+  const Seg sa = bracket_window<WIN_ALPHA_LO, WIN_ALPHA_HI>(BP_alpha_bp, T + OFF_pair_alpha, a.alpha);
 #endif
   // 16 alpha 1-D tables, [12][16 values | 16 alpha-slopes]; FGTable 1-D semantics (clamp
   // at the ends)
@@ -1178,7 +1283,7 @@ __device__ __forceinline__ void aero(const AeroIn& a, const float* T, float* F6)
 #ifdef F16_GUESS_BRACKET
   const Seg sb13 = bracket_g_uniform(BP_beta13_bp, T + OFF_pair_beta13, a.beta);
 #else
-  const Seg sb13 = bracket(BP_beta13_bp, T + OFF_pair_beta13, a.beta);
+  const Seg sb13 = bracket_window<WIN_BETA_LO, WIN_BETA_HI>(BP_beta13_bp, T + OFF_pair_beta13, a.beta);
 #endif
   float AB13[2];  // Clb, Cnb over (alpha, beta 13)
   {
@@ -1212,7 +1317,7 @@ __device__ __forceinline__ void aero(const AeroIn& a, const float* T, float* F6)
 #ifdef F16_GUESS_BRACKET
   const Seg sm = bracket_guess<13>(T + OFF_pair_machu, a.mach, machu_u(a.mach));
 #else
-  const Seg sm = bracket(BP_machu, T + OFF_pair_machu, a.mach);
+  const Seg sm = bracket_window<WIN_MACH_LO, WIN_MACH_HI>(BP_machu, T + OFF_pair_machu, a.mach);
 #endif
   float MU[MACHU_NT];
   {
@@ -1271,9 +1376,16 @@ __device__ __forceinline__ void aero(const AeroIn& a, const float* T, float* F6)
 // 256-register build takes it)
 // WIND: the lane may carry wind (the wind kernels, IC passes); false skips the air-relative
 // velocity's wind term (reference task: no wind, jsbsim_gym.py never enables FGWinds).
-template <bool LOWREG = false, bool WIND = true>
+// LATE (the step's first frame under the counted prologue waits): called right before the FCS,
+// the first reader of the FCS / engine columns -- the caller unpacks them there, so that nothing
+// ahead of this point waits for them.
+struct NoLate {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <bool LOWREG = false, bool WIND = true, class LATE = NoLate>
 __device__ __forceinline__ void frame(Lane& L, const float* cmd, double& ce, double& se, const AltRef& A,
-                                      const float* T, const ModelConsts& C, bool ic F16_STAMP_ARG) {
+                                      const float* T, const ModelConsts& C, bool ic F16_STAMP_ARG,
+                                      const LATE& late = LATE()) {
   const float dt = C.dt_f;
   const FcsTab tb = fcs_tables(L, T);
   if (!ic) {
@@ -1389,6 +1501,10 @@ __device__ __forceinline__ void frame(Lane& L, const float* cmd, double& ce, dou
   F16_STAMP(stamps, ST_ATM);
   // -- Systems (reads the previous frame's latch) --
   FcsOut fc;
+  if constexpr (!__is_same(LATE, NoLate)) {
+    __builtin_amdgcn_sched_barrier(0);  // (the scheduler hoists no use of those columns above here)
+    late();
+  }
   fcs_run<LOWREG>(L, cmd, d.Tl2b[8], d.uvw[1], T, tb, C, dt, ic, fc);
   F16_STAMP(stamps, ST_FCS);
   // -- Propulsion --

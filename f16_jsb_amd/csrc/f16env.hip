@@ -553,6 +553,15 @@ __device__ __forceinline__ void earth_angle(double epa, double& ce, double& se) 
     asm volatile("" ::: "memory");          \
   } while (0)
 #endif
+// ... and for all but the youngest k of them (s_waitcnt vmcnt(k), k < 64 a constant; gfx9
+// encoding: vmcnt in bits 3:0 and 15:14, expcnt 6:4 and lgkmcnt 11:8 left at "no wait")
+#define VM_WAIT(k)                                                                      \
+  do {                                                                                  \
+    static_assert((k) >= 0 && (k) < 64, "vmcnt is a 6-bit count");                      \
+    asm volatile("" ::: "memory");                                                      \
+    __builtin_amdgcn_s_waitcnt(0x0F70 | ((k) & 15) | ((((k) >> 4) & 3) << 14));         \
+    asm volatile("" ::: "memory");                                                      \
+  } while (0)
 
 // LDS-DMA of 16 B per lane: lane i's 16 bytes land at lds + 16*i (gfx950 global_load_lds_dwordx4)
 __device__ __forceinline__ void dma16(const float* g, float* lds) {
@@ -756,7 +765,19 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
   const int64_t row0 = (int64_t)blockIdx.x * (4 * EPW) + wave * EPW;
   const int64_t nE = pre ? pre->n : a.E.n;
   const int rows = (int)(nE - row0 < EPW ? (nE - row0 > 0 ? nE - row0 : 0) : EPW);
-  const bool image = a.lds_image != 0;
+  // The prologue's form. Counted waits (below) for every build but those that may draw the action
+  // in-kernel (the rollout slot's and the winx): their in-kernel-action row lost 0.05-0.15 us on
+  // the same-box A/B (profiles/r07_ab_counted_waits.json), so they keep the single wait.
+#ifdef F16_PROLOGUE_ONE_WAIT  // (the form before the counted waits, for the same-box A/B)
+  constexpr bool ONE_WAIT = true;
+#else
+  constexpr bool ONE_WAIT = ROLL || (XV & XV_X) != 0;
+#endif
+  // (the windowed step keeps no stack image: its launcher sets lds_image = 0. The counted-wait
+  // builds say so at compile time -- any vector-memory operation on a path between the
+  // prologue's loads and a column's first use, even a never-taken one, turns the compiler's
+  // counted wait there into a full drain)
+  const bool image = (ONE_WAIT || !WIN) && a.lds_image != 0;
   // cfg5 modes in the windowed layout reset finished lanes in the step (reset cache)
   const bool in_step_reset = WIN && DEFER && a.icc.c != nullptr && !(a.E.flags & F16_FLAG_NO_AUTORESET);
 #ifdef F16_NO_STASH
@@ -800,76 +821,118 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
   // reading env 0 -- let the argument fetches issue before the wait too, but measured no faster
   // at 65 536 envs and 0.5 us slower for cfg5's two-wave kernel: profiles/r06_ab_prologue.json)
   float4 cl[NCOL], wl, gl;
-  if (live) {
-    if (pre) {
-      const SoA sp = {const_cast<float4*>(pre->sc), pre->n};
-      lane_fetch<GUST>(sp, k, cl, wl, gl);
-      if (!SAMPLE || !a.sample_act) av = reinterpret_cast<const float4*>(pre->act)[k];
-    } else {
-      lane_fetch<GUST>(a.s, k, cl, wl, gl);
-      if (!SAMPLE || !a.sample_act) av = reinterpret_cast<const float4*>(a.act)[k];
+  const bool load_act = !SAMPLE || !a.sample_act;
+  constexpr bool C15_EARLY = GUST || STASH;  // builds that read C15 before the frames (FETCH_ORDER)
+  if constexpr (ONE_WAIT) {
+    if (live) {
+      if (pre) {
+        const SoA sp = {const_cast<float4*>(pre->sc), pre->n};
+        lane_fetch<GUST>(sp, k, cl, wl, gl);
+        if (load_act) av = reinterpret_cast<const float4*>(pre->act)[k];
+      } else {
+        lane_fetch<GUST>(a.s, k, cl, wl, gl);
+        if (load_act) av = reinterpret_cast<const float4*>(a.act)[k];
+      }
     }
-  }
-  VM_DRAIN();
+    VM_DRAIN();
 #ifndef F16_PROLOGUE_NO_SCHED_BARRIER  // (for the same-box A/B)
-  __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
 #endif
-  if (live) lane_unpack<GUST>(cl, wl, gl, L);
-  __syncthreads();
-  issue_stack_dma();
+    if (live) lane_unpack<GUST>(cl, wl, gl, L);
+    __syncthreads();
+  } else {
+    // Counted waits: the columns are issued in the order of their first use (FETCH_ORDER) and
+    // nothing drains them here. Each first use waits with the compiler's own s_waitcnt vmcnt(k),
+    // k the loads issued behind that column, so the Earth angle, the altitude reference, the
+    // recomputed latch and the head of the first frame run while the late columns (FCS / engine
+    // state, the action, C15) still arrive; C15 is first read by the env layer after the frames.
+    // The loads are unconditional -- a lane past the end reads the last env's row and drops it --
+    // so every wave issues the same number of them, which the counted wait below relies on, and
+    // the loaded values reach their uses without a merge at the end of a branch (the optimiser
+    // moves a merged value's first operation up into the branch, next to the loads, where it
+    // waits for its column with every later load still to issue).
+    {
+      // (the addresses through an empty asm: the preloaded ones are __restrict__ kernel
+      // arguments, and loads from such memory may be moved anywhere -- the compiler sank ten of
+      // the columns below the barrier, behind a full drain for the first seven)
+      float4* scp = pre ? const_cast<float4*>(pre->sc) : a.s.c;
+      const float* actp = pre ? pre->act : a.act;
+      asm volatile("" : "+s"(scp), "+s"(actp));
+      // (... and back into the global address space, which the asm forgets: a generic pointer
+      // loads with flat_load, which may hit LDS and so waits for the DMAs first)
+      const GCol scg = (GCol)scp, actg = (GCol)actp;
+      const int64_t kc = k < nE ? k : (nE > 0 ? nE - 1 : 0);
+      lane_fetch_ordered<GUST, C15_EARLY, 0>(scg, pre ? pre->n : a.s.n, kc, cl, wl, gl);
+      if (load_act) av = fetch_col(actg + kc);
+      lane_fetch_ordered<GUST, C15_EARLY, 1>(scg, pre ? pre->n : a.s.n, kc, cl, wl, gl);
+    }
+    // (every load above is issued before any wait: the count below says how many were)
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    // The barrier below publishes the table / template staging, so this wave's own LDS-DMAs must
+    // have landed. They are the oldest entries: vmcnt(k), k no more than the number of loads
+    // issued behind them, retires them and leaves the state columns in flight. k counts the 16
+    // (18) columns and not the action: builds that may draw the action in-kernel issue its load
+    // or not (a run-time choice, one count less again for them), and the one load more this
+    // retires is the first column, C13, which the frame's first instructions read anyway. (One
+    // unconditional wait: after a branch between two counts the compiler drains everything at
+    // the barrier.)
+    if (!GT || !DEFER) VM_WAIT(NCOL + (GUST ? 2 : 0) - (SAMPLE ? 1 : 0));
+    __syncthreads();
+    // (no first use hoisted between the wait and the barrier: the compiler's own wait for it
+    // there came out as a full drain)
+    __builtin_amdgcn_sched_barrier(0);
+    // (every lane unpacks what it loaded, a lane past the end its copy of the last env's row:
+    // under "if (live)" the unpacked values would merge with nothing at the branch's end, and the
+    // copies that merge makes read every column there)
+    lane_unpack<GUST, 1>(cl, wl, gl, L);
+  }
+  // (counted waits: the stack and fresh-frame DMAs go behind the first frame, below, for the
+  // reason given at `image` above; they still stream in under the other frames)
+  if constexpr (ONE_WAIT) issue_stack_dma();
   if (SAMPLE && a.sample_act && live) av = philox_action(a.act_seed, (uint64_t)(a.E.id_base + k), a.act_step);
   // a lane reset since the last step: the windowed step reads its reset frame (wy[p-1]) now,
   // so the load streams in behind the physics
   // (LDS-DMA into the wave's staging area, [15][64] floats, not registers: nothing stays live
   // across the frames; the vmcnt(0) after the frames retires it)
+  double ce = 1.0, se = 0.0;
+  AltRef A;
+  if constexpr (!ONE_WAIT) {
+    // the Earth angle and the exact geodetic altitude (once per env step) from the first columns,
+    // ahead of the first read of C14 below (every lane, as the unpack)
+    earth_angle(L.epa, ce, se);
+    A = alt_ref(L, ce, se);
+    __builtin_amdgcn_sched_barrier(0);
+    lane_unpack<GUST, 2>(cl, wl, gl, L);
+  }
   bool fresh = false;
   float* stg = dynl + (size_t)wave * WIN_WAVE_FLOATS;
-  if (live) {
-    fresh = (L.flags & LANE_FLAG_FRESH) != 0;
+  if constexpr (ONE_WAIT) {
+    if (live) {
+      fresh = (L.flags & LANE_FLAG_FRESH) != 0;
+      L.flags &= ~LANE_FLAG_FRESH;
+    }
+  } else {  // (every lane, as the unpack: no merge at a branch's end)
+    fresh = live && (L.flags & LANE_FLAG_FRESH) != 0;
     L.flags &= ~LANE_FLAG_FRESH;
   }
-  if (WIN && fresh && a.E.K > 1) {
-    const float* src = a.wy + k * a.wenv + (int64_t)(a.wpos - 1) * a.wrow;
+  const auto issue_fresh_dma = [&]() {
+    if (WIN && fresh && a.E.K > 1) {
+      const float* src = a.wy + k * a.wenv + (int64_t)(a.wpos - 1) * a.wrow;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) dma16(src + 4 * j, stg + j * 256);  // [j][lane] float4
-  }
+      for (int j = 0; j < 4; ++j) dma16(src + 4 * j, stg + j * 256);  // [j][lane] float4
+    }
+  };
+  if constexpr (ONE_WAIT) issue_fresh_dma();
   F16_STAMP(stamps, ST_LOAD);
   float f[F16_OBS_DIM], f0[F16_OBS_DIM];
   float rew_out = 0.0f;
   int flags_out = 0;
-  double ce = 1.0, se = 0.0;
-  AltRef A;
-  if (live) {
-    const float4 ac = (ROLL && a.clip_act) ? clip_box(av) : av;  // the env steps the clipped action
-    const float cmd[4] = {ac.x, ac.y, ac.z, ac.w};
-    L.step += 1;                                              // jsbsim_gym.py:215
-    if (GUST) {  // cfg5 Gauss-Markov gust update, once per env step before the frames
-      float xi[3];
-      rng_normals(a.E.seed, (uint64_t)(a.E.id_base + k), (uint32_t)(L.ep_count - 1), (uint32_t)L.step, xi);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        L.gust[j] = __builtin_fmaf(a.E.gust_a, L.gust[j], a.E.gust_b * xi[j]);  // explicit: every build alike
-        L.wind[j] = L.wst[j] + L.gust[j];
-      }
-    }
-    earth_angle(L.epa, ce, se);
-    A = alt_ref(L, ce, se);  // exact geodetic altitude once per env step
-    F16_STAMP(stamps, ST_ENVPRE);
-    // 256-register windowed builds: the env fields the frames never read (goal, last distance,
-    // step, episode count and return) wait in the wave's LDS stash instead of VGPRs, which the
-    // frame loop needs (they were part of what spilled to scratch around it)
-    float4* stash = reinterpret_cast<float4*>(stg + WFRESH);
-    if (STASH) {
-      stash[lane] = make_float4(L.goal[0], L.goal[1], L.goal[2], L.last_d);
-      stash[64 + lane] = make_float4(__int_as_float(L.step), __int_as_float(L.ep_count), dlo(L.ep_ret), dhi(L.ep_ret));
-      // the Earth angle: the frames advance it by a constant each (replayed below, the same
-      // fp64 adds) and otherwise read only its cos / sin; the gust model's pieces: the frames
-      // read the wind sum only
-      stash[128 + lane] = make_float4(dlo(L.epa), dhi(L.epa), GUST ? L.gust[0] : 0.0f, GUST ? L.gust[1] : 0.0f);
-      if (GUST) stash[192 + lane] = make_float4(L.gust[2], L.wst[0], L.wst[1], L.wst[2]);
-      asm volatile("" ::: "memory");
-    }
-    for (int s = 0; s < a.E.down_sample; ++s)  // :225-232
+  float cmd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  float4* stash = reinterpret_cast<float4*>(stg + WFRESH);
+  // the frames from s0 on, and what follows them in the 256-register windowed builds
+  const auto rest_frames = [&](int s0) {
+    for (int s = s0; s < a.E.down_sample; ++s)  // :225-232
       frame<LOWREG, GUST>(L, cmd, ce, se, A, sT, a.C, false F16_STAMP_PASS);
     if (STASH) {
       asm volatile("" ::: "memory");
@@ -883,6 +946,71 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
         const float4 u = stash[192 + lane];
         L.gust[0] = w.z; L.gust[1] = w.w; L.gust[2] = u.x; L.wst[0] = u.y; L.wst[1] = u.z; L.wst[2] = u.w;
       }
+    }
+  };
+#ifdef F16_PROLOGUE_NO_PEEL  // (for the same-box A/B: every frame in the loop)
+  const int peeled = 0;
+#else
+  const int peeled = (!ONE_WAIT && a.E.down_sample > 0) ? 1 : 0;
+#endif
+  // what a step does ahead of its frames
+  const auto pre_frames = [&]() {
+    const float4 ac = (ROLL && a.clip_act) ? clip_box(av) : av;  // the env steps the clipped action
+    cmd[0] = ac.x; cmd[1] = ac.y; cmd[2] = ac.z; cmd[3] = ac.w;
+    L.step += 1;                                              // jsbsim_gym.py:215
+    if (GUST) {  // cfg5 Gauss-Markov gust update, once per env step before the frames
+      float xi[3];
+      rng_normals(a.E.seed, (uint64_t)(a.E.id_base + k), (uint32_t)(L.ep_count - 1), (uint32_t)L.step, xi);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        L.gust[j] = __builtin_fmaf(a.E.gust_a, L.gust[j], a.E.gust_b * xi[j]);  // explicit: every build alike
+        L.wind[j] = L.wst[j] + L.gust[j];
+      }
+    }
+    if constexpr (ONE_WAIT) {
+      earth_angle(L.epa, ce, se);
+      A = alt_ref(L, ce, se);  // exact geodetic altitude once per env step
+    }
+    F16_STAMP(stamps, ST_ENVPRE);
+    // 256-register windowed builds: the env fields the frames never read (goal, last distance,
+    // step, episode count and return) wait in the wave's LDS stash instead of VGPRs, which the
+    // frame loop needs (they were part of what spilled to scratch around it)
+    if (STASH) {
+      stash[lane] = make_float4(L.goal[0], L.goal[1], L.goal[2], L.last_d);
+      stash[64 + lane] = make_float4(__int_as_float(L.step), __int_as_float(L.ep_count), dlo(L.ep_ret), dhi(L.ep_ret));
+      // the Earth angle: the frames advance it by a constant each (replayed below, the same
+      // fp64 adds) and otherwise read only its cos / sin; the gust model's pieces: the frames
+      // read the wind sum only
+      stash[128 + lane] = make_float4(dlo(L.epa), dhi(L.epa), GUST ? L.gust[0] : 0.0f, GUST ? L.gust[1] : 0.0f);
+      if (GUST) stash[192 + lane] = make_float4(L.gust[2], L.wst[0], L.wst[1], L.wst[2]);
+      asm volatile("" ::: "memory");
+    }
+  };
+  if constexpr (ONE_WAIT) {
+    if (live) {
+      pre_frames();
+      rest_frames(0);
+    }
+  } else {
+    // Every lane runs the step's head and its first frame, a lane past the end on its copy of the
+    // last env's row (dropped at the stores): entering a branch here, the register allocator
+    // parks what the frames do not read (C15, parts of C12) in other registers at the branch's
+    // head, and those copies wait for the last load. The first frame stands apart from the
+    // loop: straight-line code behind the prologue, in which each late column's first use
+    // carries its own counted wait (inside the loop the columns are loop-carried values, copied
+    // -- and so waited for -- at its head). It unpacks the FCS / engine columns where the FCS
+    // first reads them.
+    pre_frames();
+    const auto late = [&]() { lane_unpack<GUST, 3>(cl, wl, gl, L); };
+    if (peeled)
+      frame<LOWREG, GUST>(L, cmd, ce, se, A, sT, a.C, false F16_STAMP_PASS, late);
+    else
+      late();
+    // (the stack DMA is the whole wave's, whatever its live lanes)
+    if constexpr (!WIN) issue_stack_dma();
+    if (live) {
+      issue_fresh_dma();
+      rest_frames(peeled);
     }
   }
   // Early state store, with no done list to compact (its atomic's return would wait for every
