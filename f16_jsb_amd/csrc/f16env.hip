@@ -19,9 +19,6 @@
 
 #include "../../include/f16env.h"
 #include "f16_device.h"
-#ifndef F16_C15_ALWAYS
-#define F16_C15_ALWAYS 0
-#endif
 
 using namespace f16;
 
@@ -496,16 +493,12 @@ __device__ __forceinline__ void lane_reset_template(Lane& L, const float4* sTmpl
   L.step = 0;
   L.ep_ret = 0.0;
   L.flags |= LANE_FLAG_FRESH;
-#ifdef F16_RESET_MAKE_FRAME  // A/B only: evaluate frame 0 per finished lane
-  make_frame(L, 1.0, 0.0, alt_ref(L, 1.0, 0.0), f0);
-#else
 #pragma unroll
   for (int j = 0; j < TMPL_FRAME_COLS; ++j) {
     const float4 v = sTmpl[NCOL + j];
     f0[4 * j] = v.x; f0[4 * j + 1] = v.y; f0[4 * j + 2] = v.z; f0[4 * j + 3] = v.w;
   }
   f0[12] = L.goal[0]; f0[13] = L.goal[1]; f0[14] = L.goal[2];
-#endif
   L.last_d = norm3f(f0[12] - f0[0], f0[13] - f0[1], f0[14] - f0[2]);
 }
 
@@ -536,6 +529,10 @@ __device__ __forceinline__ void earth_angle(double epa, double& ce, double& se) 
 #ifndef IMG_OFF
 #define IMG_OFF 0
 #endif
+// loads in flight per lane and chunk of the large-K fallback's flat copy (step_body)
+#ifndef F16_FALLBACK_CH
+#define F16_FALLBACK_CH 16
+#endif
 
 // Wait for every outstanding vector-memory operation (s_waitcnt vmcnt(0)) as the compiler's
 // own wait: its wait-insertion pass then knows the LDS-DMA issued before is retired. (An
@@ -543,16 +540,12 @@ __device__ __forceinline__ void earth_angle(double epa, double& ce, double& se) 
 // staging area as pending and put another vmcnt(0) before the slot staging's LDS writes --
 // which on CDNA also waits for every state store issued in between.) The empty asm statements
 // keep the compiler from moving memory operations across it.
-#ifdef F16_ASM_VMCNT  // (round 5's form, for the same-box A/B)
-#define VM_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
 #define VM_DRAIN()                          \
   do {                                      \
     asm volatile("" ::: "memory");          \
     __builtin_amdgcn_s_waitcnt(0x0F70);     \
     asm volatile("" ::: "memory");          \
   } while (0)
-#endif
 // ... and for all but the youngest k of them (s_waitcnt vmcnt(k), k < 64 a constant; gfx9
 // encoding: vmcnt in bits 3:0 and 15:14, expcnt 6:4 and lgkmcnt 11:8 left at "no wait")
 #define VM_WAIT(k)                                                                      \
@@ -582,11 +575,7 @@ __device__ __forceinline__ void stage_tables_issue(float* sT) {
   // stride BLOCK, not blockDim.x: every kernel that stages the tables launches BLOCK threads, and
   // blockDim.x is a load from the implicit kernel arguments -- the wait for it held the DMA (and
   // the state loads behind it) until the whole argument block had arrived
-#ifdef F16_STAGE_BLOCKDIM  // (round 5's form, for the same-box A/B)
-  for (int r = 0; r < NP; r += blockDim.x) {
-#else
   for (int r = 0; r < NP; r += BLOCK) {
-#endif
     const int piece = r + threadIdx.x;
     if (piece < NP) dma16(F16_BLOB_INIT + 4 * piece, sT + 4 * (r + wave_base));
   }
@@ -665,7 +654,6 @@ struct StepArgs {
   int64_t wrow;                // floats between positions (position-major: N * 16; env-major: 16)
   int64_t wenv;                // floats between envs (position-major: 16; env-major: T * 16)
   int32_t wpos;                // newest frame position p (window = p-K+1 .. p)
-  int32_t half_delay;          // HALF builds (experiment): cycles the second half of the grid waits
   // the feature window in the rollout-slot build (F16_SLOT_FEATURE_WINDOW): the feature
   // histories [T][N][17] of this step's parity (fwx) and the other (fwy); nullptr: none
   float* fwx;
@@ -721,6 +709,100 @@ static constexpr int WFRESH = 16 * 64;  // LDS floats per wave for the fresh-fra
 static constexpr int WSTASH = 16 * 64;  // ... and for the env-field stash of the 256-register builds
 static constexpr int WIN_WAVE_FLOATS = WFRESH + WSTASH;
 
+// ------------------------------------------------------------------------------------------
+// Pieces of step_body's epilogue (what a wave writes after its reward and state stores). `stg` is
+// the wave's LDS staging area (WIN_WAVE_FLOATS), `img` its stack image.
+// Only what leaves every kernel's instruction stream as it was stands here (tools/isa_diff.py
+// against the in-line form). The three layout arms themselves -- window, LDS image, large-K
+// fallback -- and the feature window stay in line in step_body: a function is simplified on its
+// own before it is inlined, and one that reads the lane's frames (f, f0: registers in step_body,
+// memory behind a pointer argument) or computes under `if (live)` came out as other code in every
+// kernel that carries it, the headline instances included.
+// ------------------------------------------------------------------------------------------
+// A lane's frame slot into the staging area, transposed for the wave's slot stores: quarter j
+// of slot r at float4 r*4 + (j ^ (r>>2 & 3)), conflict-free on both the per-lane writes here and
+// the per-slot reads
+__device__ __forceinline__ void stage_slot(float4* st4, int lane, int sw, const float* fr) {
+  st4[lane * 4 + (0 ^ sw)] = make_float4(fr[0], fr[1], fr[2], fr[3]);
+  st4[lane * 4 + (1 ^ sw)] = make_float4(fr[4], fr[5], fr[6], fr[7]);
+  st4[lane * 4 + (2 ^ sw)] = make_float4(fr[8], fr[9], fr[10], fr[11]);
+  st4[lane * 4 + (3 ^ sw)] = make_float4(fr[12], fr[13], fr[14], 0.0f);
+}
+// A full wave's 64 rows of PITCH floats leave through its staging area (free after the frame
+// stores) as one contiguous block. Each lane writes its row at a PITCH-float pitch (the frames'
+// 15 and the features' 17 are odd: conflict-free) ...
+template <int PITCH>
+__device__ __forceinline__ void wave_rows_stage(float* stg, int lane, const float* vals) {
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int j = 0; j < PITCH; ++j) stg[lane * PITCH + j] = vals[j];
+  __builtin_amdgcn_wave_barrier();
+}
+// ... then 16 * PITCH float4 go out linearly to d0 (TWO: and d1, from the same LDS read); a
+// destination whose rows are not 16-B aligned (N % 4 != 0) takes dword stores
+template <int PITCH, bool TWO = false>
+__device__ __forceinline__ void wave_rows_out(const float* stg, int lane, float* d0, float* d1 = nullptr) {
+  const uintptr_t both = TWO ? (((uintptr_t)d0) | ((uintptr_t)d1)) : (uintptr_t)d0;
+  if ((both & 15) == 0) {
+    for (int u = lane; u < 64 * PITCH / 4; u += 64) {
+      const float4 v = reinterpret_cast<const float4*>(stg)[u];
+      reinterpret_cast<float4*>(d0)[u] = v;
+      if (TWO) reinterpret_cast<float4*>(d1)[u] = v;
+    }
+  } else {
+    for (int u = lane; u < 64 * PITCH; u += 64) {
+      d0[u] = stg[u];
+      if (TWO) d1[u] = stg[u];
+    }
+  }
+}
+
+// Rollout slot frame, contiguous layout = the newest frame of obs_prev (what the policy acted
+// on), for every lane of the wave (the windowed build writes the returned observation's newest
+// frame instead: r_next_frame)
+__device__ __forceinline__ void r_frame_out(const StepArgs& a, const float* img, bool image, int lane, int rows,
+                                            int64_t row0, int64_t k, bool live, int KC, int HC) {
+  if (image) {
+    __builtin_amdgcn_wave_barrier();
+    float* dst = a.r_frame + row0 * F16_OBS_DIM;
+    if (rows == 64) {  // 960 floats = 240 float4, 16-B aligned (row0 is a multiple of 64)
+      for (int q = lane; q < 64 * F16_OBS_DIM / 4; q += 64) {
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int j = 4 * q + i, r = j / F16_OBS_DIM, c = j - r * F16_OBS_DIM;
+          v[i] = img[IMG_OFF + r * KC + HC + c];
+        }
+        reinterpret_cast<float4*>(dst)[q] = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    } else {
+      for (int j = lane; j < rows * F16_OBS_DIM; j += 64) {
+        const int r = j / F16_OBS_DIM, c = j - r * F16_OBS_DIM;
+        dst[j] = img[IMG_OFF + r * KC + HC + c];
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  } else if (live) {
+#pragma unroll
+    for (int c = 0; c < F16_OBS_DIM; ++c) a.r_frame[k * F16_OBS_DIM + c] = a.obs_prev[k * KC + HC + c];
+  }
+}
+
+// The pose export (F16_STEP_POSES, f16_poses_kernel's output written here instead of by a
+// second launch): po, the pose of the returned observation's newest frame (computed by the
+// caller, see above); the wave's 64 rows are 640 contiguous floats
+__device__ __forceinline__ void pose_epilogue(const StepArgs& a, float* stg, int lane, int rows, int64_t row0,
+                                              int64_t k, bool live, const float* po) {
+  if (rows == 64) {
+    wave_rows_stage<10>(stg, lane, po);
+    wave_rows_out<10>(stg, lane, a.poses + row0 * 10);
+    __builtin_amdgcn_wave_barrier();
+  } else if (live) {
+#pragma unroll
+    for (int j = 0; j < 10; ++j) a.poses[k * 10 + j] = po[j];
+  }
+}
+
 // The prologue's first loads from kernel arguments preloaded into SGPRs (StepPre, windowed
 // kernels): the state, action and template addresses and N are in registers when the wave
 // starts, so the state / action loads and the table and template DMA issue without first
@@ -731,10 +813,6 @@ struct StepPre {
   const float4* tmpl;
   int64_t n;
 };
-// HALF (windowed builds, an experiment: F16ENV_HALF=1): 32 envs per wave in lanes 0-31, so a
-// grid of N envs is N/32 waves -- two per SIMD at 65 536 envs -- and the second half of the
-// grid may start `half_delay` cycles late, so that one wave's memory phases (prologue loads,
-// store tail) overlap the other's frames on the same SIMD.
 // XV (windowed plain-step extras, f16_step_winx_kernel / f16env_window_step_ex): XV_FEAT keeps the
 // bound feature histories in the step's epilogue (the rollout-slot build's F16_SLOT_FEATURE_WINDOW
 // code, without the slot); every winx build draws the actions in-kernel when act == NULL
@@ -743,7 +821,7 @@ struct StepPre {
 // carry none of this code.
 enum { XV_X = 1, XV_FEAT = 2 };
 template <int MODE, bool GT = false, bool ROLL = false, bool LOWREG = false, bool WIN = false, bool NT = false,
-          bool HALF = false, int XV = 0>
+          int XV = 0>
 __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, float4* sTmpl, int* sDone, float* dynl,
                                           const StepPre* pre = nullptr) {
   const float* sT = GT ? static_cast<const float*>(F16_BLOB_INIT) : sT_lds;
@@ -751,20 +829,15 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
   // builds that may draw the actions in-kernel (act == NULL): the rollout slot's and the winx
   constexpr bool SAMPLE = ROLL || (XV & XV_X) != 0;
   constexpr bool FEATW = ROLL || (XV & XV_FEAT) != 0;  // builds with the feature-window epilogue
-  constexpr int EPW = HALF ? 32 : 64;  // envs per wave
 #ifdef F16_STAMPS
   Stamps stamps = {};
   stamps.last = memtime();
 #endif
-  if (HALF && a.half_delay > 0 && blockIdx.x >= gridDim.x / 2) {
-    const uint64_t t0 = __builtin_amdgcn_s_memtime();
-    while (__builtin_amdgcn_s_memtime() - t0 < (uint64_t)a.half_delay) __builtin_amdgcn_s_sleep(8);
-  }
   const int KC = a.E.K * F16_OBS_DIM, HC = (a.E.K - 1) * F16_OBS_DIM;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t row0 = (int64_t)blockIdx.x * (4 * EPW) + wave * EPW;
+  const int64_t row0 = (int64_t)blockIdx.x * BLOCK + wave * 64;
   const int64_t nE = pre ? pre->n : a.E.n;
-  const int rows = (int)(nE - row0 < EPW ? (nE - row0 > 0 ? nE - row0 : 0) : EPW);
+  const int rows = (int)(nE - row0 < 64 ? (nE - row0 > 0 ? nE - row0 : 0) : 64);
   // The prologue's form. Counted waits (below) for every build but those that may draw the action
   // in-kernel (the rollout slot's and the winx): their in-kernel-action row lost 0.05-0.15 us on
   // the same-box A/B (profiles/r07_ab_counted_waits.json), so they keep the single wait.
@@ -780,11 +853,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
   const bool image = (ONE_WAIT || !WIN) && a.lds_image != 0;
   // cfg5 modes in the windowed layout reset finished lanes in the step (reset cache)
   const bool in_step_reset = WIN && DEFER && a.icc.c != nullptr && !(a.E.flags & F16_FLAG_NO_AUTORESET);
-#ifdef F16_NO_STASH
-  constexpr bool STASH = false;
-#else
   constexpr bool STASH = LOWREG && WIN;
-#endif
   float* img = dynl + (size_t)wave * image_floats_per_wave(KC);
   // 1) DMA of this wave's previous stack block into LDS (overlaps the physics)
   auto issue_stack_dma = [&]() {
@@ -800,7 +869,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
     }
   };
   const int64_t k = row0 + lane;
-  const bool live = (!HALF || lane < EPW) && k < nE;
+  const bool live = k < nE;
   F16_CHECK(rows >= 0 && rows <= 64 && (!live || row0 + lane < nE), DBG_STATE_INDEX);
   if (WIN) F16_CHECK(a.wpos >= a.E.K - 1 && a.wpos >= 0, DBG_WINDOW_POS);
   int done = 0;
@@ -835,9 +904,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
       }
     }
     VM_DRAIN();
-#ifndef F16_PROLOGUE_NO_SCHED_BARRIER  // (for the same-box A/B)
     __builtin_amdgcn_sched_barrier(0);
-#endif
     if (live) lane_unpack<GUST>(cl, wl, gl, L);
     __syncthreads();
   } else {
@@ -948,11 +1015,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
       }
     }
   };
-#ifdef F16_PROLOGUE_NO_PEEL  // (for the same-box A/B: every frame in the loop)
-  const int peeled = 0;
-#else
   const int peeled = (!ONE_WAIT && a.E.down_sample > 0) ? 1 : 0;
-#endif
   // what a step does ahead of its frames
   const auto pre_frames = [&]() {
     const float4 ac = (ROLL && a.clip_act) ? clip_box(av) : av;  // the env steps the clipped action
@@ -1097,10 +1160,9 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
     }
     F16_STAMP(stamps, ST_RESET);
     // C15 (goal, episode count) changes only in a reset: written back for the lanes reset here
-    // (F16_C15_ALWAYS=1: every lane, the A/B reference)
     const bool reset_here = done && (!DEFER || in_step_reset) && !(a.E.flags & F16_FLAG_NO_AUTORESET);
     if (!early_store || reset_here)
-      lane_store<GUST, 0, NT>(a.s, k, L, F16_C15_ALWAYS || reset_here);  // every column (a lane reset just now rewrites its row)
+      lane_store<GUST, 0, NT>(a.s, k, L, reset_here);  // every column (a lane reset just now rewrites its row)
     else
       lane_store<GUST, 2, NT>(a.s, k, L, false);  // the rest
     F16_STAMP(stamps, ST_STORE);
@@ -1109,35 +1171,8 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
   // deferred modes: f16_reset_done_kernel rewrites finished rows after this kernel, unless the
   // windowed step resets them itself (in_step_reset)
   const bool autoreset = (!DEFER || in_step_reset) && !(a.E.flags & F16_FLAG_NO_AUTORESET);
-  // rollout slot frame = newest frame of obs_prev (what the policy acted on), for every lane
-  // (contiguous layout; the windowed build writes the returned observation's newest frame
-  // below, r_next_frame)
-  if (ROLL && !WIN && a.r_frame && rows > 0) {
-    if (image) {
-      __builtin_amdgcn_wave_barrier();
-      float* dst = a.r_frame + row0 * F16_OBS_DIM;
-      if (rows == 64) {  // 960 floats = 240 float4, 16-B aligned (row0 is a multiple of 64)
-        for (int q = lane; q < 64 * F16_OBS_DIM / 4; q += 64) {
-          float v[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int j = 4 * q + i, r = j / F16_OBS_DIM, c = j - r * F16_OBS_DIM;
-            v[i] = img[IMG_OFF + r * KC + HC + c];
-          }
-          reinterpret_cast<float4*>(dst)[q] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-      } else {
-        for (int j = lane; j < rows * F16_OBS_DIM; j += 64) {
-          const int r = j / F16_OBS_DIM, c = j - r * F16_OBS_DIM;
-          dst[j] = img[IMG_OFF + r * KC + HC + c];
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    } else if (live) {
-#pragma unroll
-      for (int c = 0; c < F16_OBS_DIM; ++c) a.r_frame[k * F16_OBS_DIM + c] = a.obs_prev[k * KC + HC + c];
-    }
-  }
+  // rollout slot frame (contiguous layout): the newest frame of obs_prev, for every lane
+  if (ROLL && !WIN && a.r_frame && rows > 0) r_frame_out(a, img, image, lane, rows, row0, k, live, KC, HC);
   if (WIN) {
     const int K = a.E.K, p = a.wpos;
     const bool reset_now = live && done && autoreset;
@@ -1159,45 +1194,35 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
     // now, else the new frame; wy: the new frame). The wave's 64 slots are one contiguous
     // 4 KiB block; the wave transposes them through its LDS staging area so that each dwordx4
     // store instruction writes 1 KiB contiguous (16 whole slots, 4 lanes per slot) instead of a
-    // 16-B quarter of every slot. Swizzle: quarter j of slot r at float4 r*4 + (j ^ (r>>2 & 3)),
-    // conflict-free on both the per-lane writes and the per-slot reads.
+    // 16-B quarter of every slot (stage_slot's swizzle).
     // A wave none of whose lanes was reset now (~94 % of waves in the bench's steady state) has
     // the same 64 slots for both histories: one LDS staging pass, each transposed float4 read
     // once and stored twice (round 6; was two passes for every wave: 4 ds_write_b128 + 4
     // ds_read_b128 and two wave barriers per wave per step saved). The byte count is unchanged:
     // both histories must hold every frame for the (N, K, 15) strided view to alternate parity
     // (DESIGN.md 9 item 7).
-#ifdef F16_TWO_PASS_SLOTS  // (A/B reference: round 5's two staging passes for every wave)
-    const bool one_pass = false;
-#else
-    const bool one_pass = !ROLL && rows == EPW && __ballot(reset_now) == 0;
-#endif
+    const bool one_pass = !ROLL && rows == 64 && __ballot(reset_now) == 0;
     if (one_pass) {
       float4* st4 = reinterpret_cast<float4*>(stg);
       const int q = lane & 3, sw = (lane >> 2) & 3;
       __builtin_amdgcn_wave_barrier();
-      st4[lane * 4 + (0 ^ sw)] = make_float4(f[0], f[1], f[2], f[3]);
-      st4[lane * 4 + (1 ^ sw)] = make_float4(f[4], f[5], f[6], f[7]);
-      st4[lane * 4 + (2 ^ sw)] = make_float4(f[8], f[9], f[10], f[11]);
-      st4[lane * 4 + (3 ^ sw)] = make_float4(f[12], f[13], f[14], 0.0f);
+      stage_slot(st4, lane, sw, f);
       __builtin_amdgcn_wave_barrier();
       const int64_t off = (int64_t)p * a.wrow + (row0 + (lane >> 2)) * a.wenv + 4 * q;
       float* const dx = a.wx + off;
       float* const dy = a.wy + off;
-      float4 v[EPW / 16];
+      float4 v[4];
 #pragma unroll
-      for (int j = 0; j < EPW / 16; ++j) {
+      for (int j = 0; j < 4; ++j) {
         const int r = 16 * j + (lane >> 2);
         v[j] = st4[r * 4 + (q ^ ((r >> 2) & 3))];
       }
 #pragma unroll
-      for (int j = 0; j < EPW / 16; ++j) st16<NT>(reinterpret_cast<float4*>(dx + (int64_t)(16 * j) * a.wenv), v[j]);
-#ifndef F16_DIAG_ONE_HIST  // (timing-only bound of a single history: wrong results by design, never shipped)
+      for (int j = 0; j < 4; ++j) st16<NT>(reinterpret_cast<float4*>(dx + (int64_t)(16 * j) * a.wenv), v[j]);
 #pragma unroll
-      for (int j = 0; j < EPW / 16; ++j) st16<NT>(reinterpret_cast<float4*>(dy + (int64_t)(16 * j) * a.wenv), v[j]);
-#endif
+      for (int j = 0; j < 4; ++j) st16<NT>(reinterpret_cast<float4*>(dy + (int64_t)(16 * j) * a.wenv), v[j]);
       __builtin_amdgcn_wave_barrier();
-    } else if (rows == EPW) {
+    } else if (rows == 64) {
       float4* st4 = reinterpret_cast<float4*>(stg);
       const int q = lane & 3, sw = (lane >> 2) & 3;
       float* const hist[2] = {a.wx, a.wy};
@@ -1205,35 +1230,19 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
       for (int h = 0; h < 2; ++h) {
         const float* fr = (h == 0 && reset_now) ? f0 : f;
         __builtin_amdgcn_wave_barrier();
-        st4[lane * 4 + (0 ^ sw)] = make_float4(fr[0], fr[1], fr[2], fr[3]);
-        st4[lane * 4 + (1 ^ sw)] = make_float4(fr[4], fr[5], fr[6], fr[7]);
-        st4[lane * 4 + (2 ^ sw)] = make_float4(fr[8], fr[9], fr[10], fr[11]);
-        st4[lane * 4 + (3 ^ sw)] = make_float4(fr[12], fr[13], fr[14], 0.0f);
+        stage_slot(st4, lane, sw, fr);
         __builtin_amdgcn_wave_barrier();
         float* dst = hist[h] + (int64_t)p * a.wrow + (row0 + (lane >> 2)) * a.wenv + 4 * q;
 #pragma unroll
-        for (int j = 0; j < EPW / 16; ++j) {
+        for (int j = 0; j < 4; ++j) {
           const int r = 16 * j + (lane >> 2);
           st16<NT>(reinterpret_cast<float4*>(dst + (int64_t)(16 * j) * a.wenv), st4[r * 4 + (q ^ ((r >> 2) & 3))]);
         }
         if (ROLL && h == 0 && a.r_next_frame) {
           // the rollout's frame log: the returned observation's newest frame (the next slot's
-          // frame), the wave's 64 rows as 960 contiguous floats: each lane writes its 15 floats
-          // at a 15-float pitch into the (now free) staging area (odd pitch: conflict-free),
-          // then 240 float4 go out linearly; a log whose rows are not 16-B aligned (N % 4 != 0)
-          // takes dword stores
-          float* sf = reinterpret_cast<float*>(st4);
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int c = 0; c < F16_OBS_DIM; ++c) sf[lane * F16_OBS_DIM + c] = fr[c];
-          __builtin_amdgcn_wave_barrier();
-          float* dstf = a.r_next_frame + row0 * F16_OBS_DIM;
-          if (((uintptr_t)dstf & 15) == 0) {
-            for (int u = lane; u < 64 * F16_OBS_DIM / 4; u += 64)
-              reinterpret_cast<float4*>(dstf)[u] = reinterpret_cast<const float4*>(sf)[u];
-          } else {
-            for (int u = lane; u < 64 * F16_OBS_DIM; u += 64) dstf[u] = sf[u];
-          }
+          // frame), the wave's 64 rows as 960 contiguous floats through the (now free) staging area
+          wave_rows_stage<F16_OBS_DIM>(stg, lane, fr);
+          wave_rows_out<F16_OBS_DIM>(stg, lane, a.r_next_frame + row0 * F16_OBS_DIM);
         }
       }
       __builtin_amdgcn_wave_barrier();
@@ -1256,26 +1265,10 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
       const int64_t rowN = a.E.n * FEAT_OUT;
       float y[FEAT_OUT];
       if (live) frame_features(reset_now ? f0 : f, y);
-      if (rows == EPW) {
-        float* sf = stg;
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int j = 0; j < FEAT_OUT; ++j) sf[lane * FEAT_OUT + j] = y[j];
-        __builtin_amdgcn_wave_barrier();
-        float* gx = a.fwx + (int64_t)p * rowN + row0 * FEAT_OUT;
-        float* gy = a.fwy + (int64_t)p * rowN + row0 * FEAT_OUT;
-        if (((((uintptr_t)gx) | ((uintptr_t)gy)) & 15) == 0) {
-          for (int u = lane; u < 64 * FEAT_OUT / 4; u += 64) {
-            const float4 v = reinterpret_cast<const float4*>(sf)[u];
-            reinterpret_cast<float4*>(gx)[u] = v;
-            reinterpret_cast<float4*>(gy)[u] = v;
-          }
-        } else {
-          for (int u = lane; u < 64 * FEAT_OUT; u += 64) {
-            gx[u] = sf[u];
-            gy[u] = sf[u];
-          }
-        }
+      if (rows == 64) {
+        wave_rows_stage<FEAT_OUT>(stg, lane, y);
+        wave_rows_out<FEAT_OUT, true>(stg, lane, a.fwx + (int64_t)p * rowN + row0 * FEAT_OUT,
+                                      a.fwy + (int64_t)p * rowN + row0 * FEAT_OUT);
         // the window fills of the wave's reset lanes (rare), each lane's (row, feature) pairs
         // spread over the whole wave from the staging area (as f16_feature_window_kernel)
         const uint64_t rm = __ballot(reset_now);
@@ -1288,7 +1281,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
               const int ri = it / FEAT_OUT, j = it - ri * FEAT_OUT;
               float* d = ri < K - 1 ? a.fwx + (int64_t)(p - K + 1 + ri) * rowN
                                     : a.fwy + (int64_t)(p - K + 2 + (ri - (K - 1))) * rowN;
-              d[kk * FEAT_OUT + j] = sf[ee * FEAT_OUT + j];
+              d[kk * FEAT_OUT + j] = stg[ee * FEAT_OUT + j];
             }
           }
         }
@@ -1300,7 +1293,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
           a.fwy[(int64_t)p * rowN + k * FEAT_OUT + j] = y[j];
         }
       }
-      if (rows != EPW && reset_now && K > 1) {  // a partial wave's reset lanes: one lane each
+      if (rows != 64 && reset_now && K > 1) {  // a partial wave's reset lanes: one lane each
         for (int r = p - K + 1; r < p; ++r) {
 #pragma unroll
           for (int j = 0; j < FEAT_OUT; ++j) {
@@ -1311,29 +1304,9 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
       }
     }
     if ((XV & XV_X) != 0 && a.poses) {
-      // the pose export (F16_STEP_POSES, f16_poses_kernel's output written here instead of by a
-      // second launch): the pose of the returned observation's newest frame; the wave's 64 rows
-      // (640 contiguous floats) leave through its staging area as float4
       float po[10];
       if (live) pose_of_frame(reset_now ? f0 : f, po);
-      if (rows == EPW) {
-        float* sp = stg;
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int j = 0; j < 10; ++j) sp[lane * 10 + j] = po[j];
-        __builtin_amdgcn_wave_barrier();
-        float* g = a.poses + row0 * 10;
-        if (((uintptr_t)g & 15) == 0) {
-          for (int u = lane; u < 64 * 10 / 4; u += 64)
-            reinterpret_cast<float4*>(g)[u] = reinterpret_cast<const float4*>(sp)[u];
-        } else {
-          for (int u = lane; u < 64 * 10; u += 64) g[u] = sp[u];
-        }
-        __builtin_amdgcn_wave_barrier();
-      } else if (live) {
-#pragma unroll
-        for (int j = 0; j < 10; ++j) a.poses[k * 10 + j] = po[j];
-      }
+      pose_epilogue(a, stg, lane, rows, row0, k, live, po);
     }
     F16_STAMP(stamps, ST_COPY);
   } else if (image) {
@@ -1406,9 +1379,6 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
       float* tout = a.tobs ? a.tobs + row0 * KC : nullptr;
       const int total = rows * KC;
       int row = lane / KC, col = lane - (lane / KC) * KC;
-#ifndef F16_FALLBACK_CH
-#define F16_FALLBACK_CH 16
-#endif
       constexpr int CH = F16_FALLBACK_CH;
       for (int base = 0; base < total; base += 64 * CH) {
         float v[CH];
@@ -1489,18 +1459,14 @@ __global__ __launch_bounds__(BLOCK, 1) void f16_step_gt_kernel(STEP_PRE_ARGS, St
 // actions, the slot's actions / rewards / next starts and the returned observation's newest
 // frame); the plain windowed step carries none of its code.
 template <int MODE, int OCC, bool ROLL = false>
-__global__ __launch_bounds__(BLOCK, OCC) void f16_step_win_kernel(const float4* __restrict__ sc, const float* __restrict__ act,
-                                                                  const float4* __restrict__ tmpl, int64_t n, StepArgs a) {
+__global__ __launch_bounds__(BLOCK, OCC) void f16_step_win_kernel(STEP_PRE_ARGS, StepArgs a) {
   STEP_SHARED
   const StepPre pre = {sc, act, tmpl, n};
   step_body<MODE, false, ROLL, OCC == 2, true>(a, sT, sTmpl, sDone, dynl, &pre);
 }
 // ... with non-temporal state and frame-slot stores, for grids resident in one round (st16)
 template <int MODE, int OCC, bool ROLL = false>
-__global__ __launch_bounds__(BLOCK, OCC) void f16_step_win_nt_kernel(const float4* __restrict__ sc,
-                                                                     const float* __restrict__ act,
-                                                                     const float4* __restrict__ tmpl, int64_t n,
-                                                                     StepArgs a) {
+__global__ __launch_bounds__(BLOCK, OCC) void f16_step_win_nt_kernel(STEP_PRE_ARGS, StepArgs a) {
   STEP_SHARED
   const StepPre pre = {sc, act, tmpl, n};
   step_body<MODE, false, ROLL, OCC == 2, true, true>(a, sT, sTmpl, sDone, dynl, &pre);
@@ -1509,23 +1475,10 @@ __global__ __launch_bounds__(BLOCK, OCC) void f16_step_win_nt_kernel(const float
 // winx build takes act == NULL as "draw the actions in-kernel"): f16env_window_step_ex. A kernel
 // of its own, so the headline instances above keep their instruction stream.
 template <int MODE, int OCC, bool NT, int XV>
-__global__ __launch_bounds__(BLOCK, OCC) void f16_step_winx_kernel(const float4* __restrict__ sc,
-                                                                   const float* __restrict__ act,
-                                                                   const float4* __restrict__ tmpl, int64_t n,
-                                                                   StepArgs a) {
+__global__ __launch_bounds__(BLOCK, OCC) void f16_step_winx_kernel(STEP_PRE_ARGS, StepArgs a) {
   STEP_SHARED
   const StepPre pre = {sc, act, tmpl, n};
-  step_body<MODE, false, false, OCC == 2, true, NT, false, XV>(a, sT, sTmpl, sDone, dynl, &pre);
-}
-// the half-populated-wave experiment (HALF above): 256-register build, two waves per SIMD
-template <int MODE>
-__global__ __launch_bounds__(BLOCK, 2) void f16_step_win_half_kernel(const float4* __restrict__ sc,
-                                                                     const float* __restrict__ act,
-                                                                     const float4* __restrict__ tmpl, int64_t n,
-                                                                     StepArgs a) {
-  STEP_SHARED
-  const StepPre pre = {sc, act, tmpl, n};
-  step_body<MODE, false, false, true, true, true, true>(a, sT, sTmpl, sDone, dynl, &pre);
+  step_body<MODE, false, false, OCC == 2, true, NT, XV>(a, sT, sTmpl, sDone, dynl, &pre);
 }
 using StepKernel = void (*)(const float4*, const float*, const float4*, int64_t, StepArgs);
 using WinKernel = StepKernel;
@@ -2425,8 +2378,6 @@ struct f16env {
   int win_occ;        // the same for the windowed-observation step kernel
   int win_env_major;  // window histories [N][T][16] (1) instead of the default [T][N][16] (0)
   int win_nt;         // windowed step: non-temporal output stores
-  int win_half;       // experiment (F16ENV_HALF=1): 32 envs per wave, f16_step_win_half_kernel
-  int half_delay;     // ... and the second half of its grid starting this many cycles late
   float* fw[2];       // f16env_window_feature_bind: the feature histories (parity 0, 1)
   float* poses;       // f16env_window_poses_bind: N x 10 pose export of F16_STEP_POSES steps
   struct {            // f16env_window_bind: the buffers of f16env_window_step_bound
@@ -2633,8 +2584,6 @@ int f16env_create(const f16env_config* cfg, int device, f16env_t* out) {
     // once (one round of waves); with more rounds they cost (st16)
     h->win_nt = waves <= (int64_t)h->win_occ * 4 * cus ? 1 : 0;
     if (getenv("F16ENV_WIN_NT")) h->win_nt = atoi(getenv("F16ENV_WIN_NT")) ? 1 : 0;
-    h->win_half = getenv("F16ENV_HALF") ? (atoi(getenv("F16ENV_HALF")) ? 1 : 0) : 0;
-    h->half_delay = getenv("F16ENV_HALF_DELAY") ? atoi(getenv("F16ENV_HALF_DELAY")) : 0;
     for (int v = 0; v <= 2; ++v) {
       const size_t st_v = v == 2 ? static_gt : static_lds;
       for (int m = 0; m < 8; ++m) {
@@ -2794,6 +2743,38 @@ static int done_counter(f16env_t h, int32_t* done_idx, int32_t*& list, int32_t*&
   return 0;
 }
 
+// One step-kernel launch: timed by the dispatch packet's own events while a profile is armed
+// (f16env_profile_*), else plain
+static int launch_step(f16env_t h, StepKernel kern, dim3 grid, size_t dyn_lds, hipStream_t st, const StepArgs& a) {
+  const dim3 blk(BLOCK);
+  const float4* sc = a.s.c;
+  const float4* tc = a.tmpl.c;
+  if (h->prof_next < (int)h->prof_ev.size() / 2) {
+    const int i = h->prof_next++;
+    hipExtLaunchKernelGGL(kern, grid, blk, (std::uint32_t)dyn_lds, st, h->prof_ev[2 * i], h->prof_ev[2 * i + 1], 0u,
+                          sc, a.act, tc, a.E.n, a);
+  } else {
+    hipLaunchKernelGGL(kern, grid, blk, dyn_lds, st, sc, a.act, tc, a.E.n, a);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// The deferred reset behind a step (cfg5 modes): f16_reset_done_kernel rewrites the rows of the
+// step's done list -- frame j of a row at obs + k * row + off + j * pitch, `slot` floats each
+static int launch_reset_done(f16env_t h, hipStream_t st, const StepArgs& a, float* obs, int64_t row, int64_t off,
+                             int64_t pitch, int32_t slot, int32_t* zero_next) {
+  ResetDoneArgs r;
+  r.s = h->soa; r.tmpl = h->tmpl; r.done_idx = a.done_idx; r.n_done = a.n_done; r.obs = obs;
+  r.obs_row = row; r.obs_off = off; r.obs_pitch = pitch; r.obs_slot = slot;
+  r.zero_next = zero_next;
+  r.E = a.E; r.C = h->C;
+  const unsigned g = nblocks(a.E.n) < 64u ? nblocks(a.E.n) : 64u;
+  hipLaunchKernelGGL(f16_reset_done_kernel, dim3(g), dim3(BLOCK), 0, st, r);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 static int step_impl(f16env_t h, void* stream, const f16env_rollout_slot* slot, const float* act,
                      const float* obs_prev, float* obs, float* rew, uint8_t* terminated, uint8_t* truncated,
                      float* terminal_obs, double* ep_return, int32_t* ep_len, int32_t* done_idx, int32_t* n_done) {
@@ -2802,27 +2783,25 @@ static int step_impl(f16env_t h, void* stream, const f16env_rollout_slot* slot, 
     return set_err(-1, "act (or a rollout slot)/obs_prev/obs/rew/terminated/truncated are required");
   if (done_idx && !n_done) return set_err(-1, "done_idx requires n_done");
   if (act && ((uintptr_t)act & 15) != 0) return set_err(-1, "act must be 16-byte aligned");
-  StepArgs a;
+  StepArgs a = {};
   a.s = h->soa; a.tmpl = h->tmpl; a.act = act; a.obs_prev = obs_prev; a.obs = obs; a.rew = rew;
   a.term = terminated; a.trunc = truncated; a.tobs = terminal_obs; a.ep_ret = ep_return; a.ep_len = ep_len;
   a.done_idx = done_idx; a.n_done = n_done;
   a.nonfinite = h->nonfinite;
   a.sample_act = act ? 0 : 1;
-  a.clip_act = (slot && (slot->flags & F16_SLOT_CLIP)) ? 1 : 0;
-  a.act_seed = slot ? slot->act_seed : 0; a.act_step = slot ? slot->act_step : 0;
-  a.r_frame = slot ? slot->frame : nullptr;
-  a.r_next_frame = nullptr;
-  a.r_act = slot ? slot->actions : nullptr;
-  a.r_rew = slot ? slot->rewards : nullptr;
-  a.r_next_start = slot ? slot->next_start : nullptr;
-  float* feat = slot ? slot->features : nullptr;
-  if (slot && slot->next_frame)
-    return set_err(-1, "rollout slot next_frame is the windowed layout's (f16env_window_step_rollout); "
-                       "the contiguous layout writes frame");
+  float* feat = nullptr;
+  if (slot) {
+    if (slot->next_frame)
+      return set_err(-1, "rollout slot next_frame is the windowed layout's (f16env_window_step_rollout); "
+                         "the contiguous layout writes frame");
+    a.clip_act = (slot->flags & F16_SLOT_CLIP) ? 1 : 0;
+    a.act_seed = slot->act_seed; a.act_step = slot->act_step;
+    a.r_frame = slot->frame; a.r_act = slot->actions; a.r_rew = slot->rewards;
+    a.r_next_start = slot->next_start;
+    feat = slot->features;
+  }
   if ((a.r_frame && ((uintptr_t)a.r_frame & 15) != 0) || (a.r_act && ((uintptr_t)a.r_act & 15) != 0))
     return set_err(-1, "rollout slot frame/actions must be 16-byte aligned");
-  a.wx = a.wy = nullptr; a.wrow = a.wenv = 0; a.wpos = 0;
-  a.icc.c = nullptr; a.icc.n = 0;
   a.E = env_args(h);
   a.C = h->C;
   a.lds_image = h->lds_image;
@@ -2831,26 +2810,11 @@ static int step_impl(f16env_t h, void* stream, const f16env_rollout_slot* slot, 
   hipStream_t st = (hipStream_t)stream;
   int32_t* zero_next = nullptr;
   if (int e = done_counter(h, done_idx, a.done_idx, a.n_done, zero_next, st)) return e;
-  const dim3 grid(nblocks(a.E.n)), blk(BLOCK);
   const StepKernel kern = step_kernel_for(h->mode, h->gt ? 2 : (h->occ == 2 ? 1 : 0), slot != nullptr);
-  if (h->prof_next < (int)h->prof_ev.size() / 2) {  // profiling: events from the dispatch packet itself
-    const int i = h->prof_next++;
-    hipExtLaunchKernelGGL(kern, grid, blk, (std::uint32_t)h->dyn_lds, st, h->prof_ev[2 * i], h->prof_ev[2 * i + 1], 0u,
-                          (const float4*)a.s.c, a.act, (const float4*)a.tmpl.c, a.E.n, a);
-  } else {
-    hipLaunchKernelGGL(kern, grid, blk, h->dyn_lds, st, (const float4*)a.s.c, a.act, (const float4*)a.tmpl.c, a.E.n, a);
-  }
-  HIPCHK(hipGetLastError());
-  if (h->mode && !(h->cfg.flags & F16_FLAG_NO_AUTORESET)) {
-    ResetDoneArgs r;
-    r.s = h->soa; r.tmpl = h->tmpl; r.done_idx = a.done_idx; r.n_done = a.n_done; r.obs = obs;
-    r.obs_row = (int64_t)a.E.K * F16_OBS_DIM; r.obs_off = 0; r.obs_pitch = F16_OBS_DIM; r.obs_slot = F16_OBS_DIM;
-    r.zero_next = zero_next;
-    r.E = a.E; r.C = h->C;
-    const unsigned g = nblocks(a.E.n) < 64u ? nblocks(a.E.n) : 64u;
-    hipLaunchKernelGGL(f16_reset_done_kernel, dim3(g), blk, 0, st, r);
-    HIPCHK(hipGetLastError());
-  }
+  if (int e = launch_step(h, kern, dim3(nblocks(a.E.n)), h->dyn_lds, st, a)) return e;
+  if (h->mode && !(h->cfg.flags & F16_FLAG_NO_AUTORESET))
+    if (int e = launch_reset_done(h, st, a, obs, (int64_t)a.E.K * F16_OBS_DIM, 0, F16_OBS_DIM, F16_OBS_DIM, zero_next))
+      return e;
   if (feat) {  // policy features of the returned obs (after any deferred reset rewrote rows)
     const int64_t nf = (int64_t)a.E.n * a.E.K;
     hipLaunchKernelGGL(f16_features_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, nf,
@@ -2912,6 +2876,21 @@ static int window_check(f16env_t h, const float* hist_cur, const float* hist_oth
   return 0;
 }
 
+// The feature window in a step's epilogue (`flag`: F16_SLOT_FEATURE_WINDOW or
+// F16_STEP_FEATURE_WINDOW, named at the head of each message): the bound feature histories of
+// this step's parity and the other
+static int feature_window_args(f16env_t h, const char* flag, const float* hist_cur, StepArgs& a) {
+  const std::string f(flag);
+  if (!h->fw[0] || !h->fw[1]) return set_err(-1, (f + ": f16env_window_feature_bind first").c_str());
+  if (hist_cur != h->wb.hist[0] && hist_cur != h->wb.hist[1])
+    return set_err(-1, (f + ": the step's histories must be the bound ones").c_str());
+  if (h->mode && !(h->cfg.flags & F16_FLAG_NO_AUTORESET) && h->icc_period <= 0)
+    return set_err(-1, (f + ": not with the deferred-reset step (F16ENV_ICC_PERIOD=0)").c_str());
+  const int b = hist_cur == h->wb.hist[0] ? 0 : 1;
+  a.fwx = h->fw[b]; a.fwy = h->fw[b ^ 1];
+  return 0;
+}
+
 static int step_window_impl(f16env_t h, void* stream, const f16env_rollout_slot* slot, const float* act,
                             float* hist_cur, float* hist_other, int64_t T, int32_t pos, float* rew,
                             uint8_t* terminated, uint8_t* truncated, double* ep_return, int32_t* ep_len,
@@ -2924,8 +2903,7 @@ static int step_window_impl(f16env_t h, void* stream, const f16env_rollout_slot*
   if (hist_cur == hist_other) return set_err(-1, "the two histories must be distinct buffers");
   if (done_idx && !n_done) return set_err(-1, "done_idx requires n_done");
   if (act && ((uintptr_t)act & 15) != 0) return set_err(-1, "act must be 16-byte aligned");
-  StepArgs a;
-  memset(&a, 0, sizeof a);
+  StepArgs a = {};
   a.s = h->soa; a.tmpl = h->tmpl; a.act = act; a.rew = rew;
   a.term = terminated; a.trunc = truncated; a.ep_ret = ep_return; a.ep_len = ep_len;
   a.done_idx = done_idx; a.n_done = n_done;
@@ -2943,15 +2921,8 @@ static int step_window_impl(f16env_t h, void* stream, const f16env_rollout_slot*
     feat = slot->features;
     if ((a.r_next_frame && ((uintptr_t)a.r_next_frame & 3) != 0) || (a.r_act && ((uintptr_t)a.r_act & 15) != 0))
       return set_err(-1, "rollout slot next_frame must be 4-byte and actions 16-byte aligned");
-    if (slot->flags & F16_SLOT_FEATURE_WINDOW) {
-      if (!h->fw[0] || !h->fw[1]) return set_err(-1, "F16_SLOT_FEATURE_WINDOW: f16env_window_feature_bind first");
-      if (hist_cur != h->wb.hist[0] && hist_cur != h->wb.hist[1])
-        return set_err(-1, "F16_SLOT_FEATURE_WINDOW: the step's histories must be the bound ones");
-      if (h->mode && !(h->cfg.flags & F16_FLAG_NO_AUTORESET) && h->icc_period <= 0)
-        return set_err(-1, "F16_SLOT_FEATURE_WINDOW: not with the deferred-reset step (F16ENV_ICC_PERIOD=0)");
-      const int b = hist_cur == h->wb.hist[0] ? 0 : 1;
-      a.fwx = h->fw[b]; a.fwy = h->fw[b ^ 1];
-    }
+    if (slot->flags & F16_SLOT_FEATURE_WINDOW)
+      if (int e = feature_window_args(h, "F16_SLOT_FEATURE_WINDOW", hist_cur, a)) return e;
   } else if (ex) {  // f16env_window_step_ex: the winx build (in-kernel actions, feature window)
     a.sample_act = act ? 0 : 1;
     a.act_seed = act_seed; a.act_step = act_step;
@@ -2963,15 +2934,8 @@ static int step_window_impl(f16env_t h, void* stream, const f16env_rollout_slot*
         return set_err(-1, "F16_STEP_POSES: not with the deferred-reset step (F16ENV_ICC_PERIOD=0)");
       a.poses = h->poses;
     }
-    if (xflags & F16_STEP_FEATURE_WINDOW) {
-      if (!h->fw[0] || !h->fw[1]) return set_err(-1, "F16_STEP_FEATURE_WINDOW: f16env_window_feature_bind first");
-      if (hist_cur != h->wb.hist[0] && hist_cur != h->wb.hist[1])
-        return set_err(-1, "F16_STEP_FEATURE_WINDOW: the step's histories must be the bound ones");
-      if (h->mode && !(h->cfg.flags & F16_FLAG_NO_AUTORESET) && h->icc_period <= 0)
-        return set_err(-1, "F16_STEP_FEATURE_WINDOW: not with the deferred-reset step (F16ENV_ICC_PERIOD=0)");
-      const int b = hist_cur == h->wb.hist[0] ? 0 : 1;
-      a.fwx = h->fw[b]; a.fwy = h->fw[b ^ 1];
-    }
+    if (xflags & F16_STEP_FEATURE_WINDOW)
+      if (int e = feature_window_args(h, "F16_STEP_FEATURE_WINDOW", hist_cur, a)) return e;
   }
   // cfg5 modes: finished lanes are reset inside the step from the reset cache (period 0 or
   // F16ENV_ICC_PERIOD=0: the deferred f16_reset_done_kernel instead)
@@ -2987,11 +2951,9 @@ static int step_window_impl(f16env_t h, void* stream, const f16env_rollout_slot*
   a.wx = hist_cur; a.wy = hist_other; a.wrow = P; a.wenv = Q; a.wpos = pos;
   a.E = env_args(h);
   a.C = h->C;
-  a.lds_image = 0;
   hipStream_t st = (hipStream_t)stream;
   int32_t* zero_next = nullptr;
-  const dim3 blk(BLOCK);
-  a.icc.c = nullptr; a.icc.n = a.E.n;
+  a.icc.n = a.E.n;
   if (cache) {
     if (int e = icc_prepare(h, st, h->icc_steps % h->icc_period == 0)) return e;
     ++h->icc_steps;
@@ -3000,37 +2962,11 @@ static int step_window_impl(f16env_t h, void* stream, const f16env_rollout_slot*
   } else if (int e = done_counter(h, done_idx, a.done_idx, a.n_done, zero_next, st)) {
     return e;
   }
-  WinKernel kern = ex ? step_winx_kernel_for(h->mode, h->win_occ, h->win_nt, a.fwx != nullptr)
-                      : step_win_kernel_for(h->mode, h->win_occ, h->win_nt, slot != nullptr);
-  dim3 grid(nblocks(a.E.n));
-  if (h->win_half && !slot && !ex) {  // the half-populated-wave experiment: 128 envs per block
-    static const WinKernel half[4] = {f16_step_win_half_kernel<0>, f16_step_win_half_kernel<1>,
-                                      f16_step_win_half_kernel<2>, f16_step_win_half_kernel<3>};
-    kern = half[h->mode & 3];
-    grid = dim3((unsigned)((a.E.n + 127) / 128));
-    a.half_delay = h->half_delay;
-  }
-  const float4* sc = a.s.c;
-  const float4* tc = a.tmpl.c;
-  const int64_t n = a.E.n;
-  if (h->prof_next < (int)h->prof_ev.size() / 2) {
-    const int i = h->prof_next++;
-    hipExtLaunchKernelGGL(kern, grid, blk, (std::uint32_t)WIN_DYN_LDS, st, h->prof_ev[2 * i], h->prof_ev[2 * i + 1], 0u,
-                          sc, a.act, tc, n, a);
-  } else {
-    hipLaunchKernelGGL(kern, grid, blk, WIN_DYN_LDS, st, sc, a.act, tc, n, a);
-  }
-  HIPCHK(hipGetLastError());
-  if (deferred) {
-    ResetDoneArgs r;
-    r.s = h->soa; r.tmpl = h->tmpl; r.done_idx = a.done_idx; r.n_done = a.n_done; r.obs = hist_cur;
-    r.obs_row = Q; r.obs_off = (int64_t)(pos - a.E.K + 1) * P; r.obs_pitch = P; r.obs_slot = WPITCH;
-    r.zero_next = zero_next;
-    r.E = a.E; r.C = h->C;
-    const unsigned g = nblocks(a.E.n) < 64u ? nblocks(a.E.n) : 64u;
-    hipLaunchKernelGGL(f16_reset_done_kernel, dim3(g), blk, 0, st, r);
-    HIPCHK(hipGetLastError());
-  }
+  const WinKernel kern = ex ? step_winx_kernel_for(h->mode, h->win_occ, h->win_nt, a.fwx != nullptr)
+                            : step_win_kernel_for(h->mode, h->win_occ, h->win_nt, slot != nullptr);
+  if (int e = launch_step(h, kern, dim3(nblocks(a.E.n)), WIN_DYN_LDS, st, a)) return e;
+  if (deferred)
+    if (int e = launch_reset_done(h, st, a, hist_cur, Q, (int64_t)(pos - a.E.K + 1) * P, P, WPITCH, zero_next)) return e;
   if (feat) {  // policy features of the returned observation, read in place from the window
     const int64_t blocks = ((int64_t)a.E.n * a.E.K + 255) / 256;
     hipLaunchKernelGGL(f16_features_strided_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (int64_t)a.E.n,

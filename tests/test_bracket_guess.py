@@ -1,4 +1,5 @@
-"""The guess-and-correct table bracket (f16_device.h bracket_guess, round 5) against FGTable's
+"""The guess-and-correct table bracket (round 5's experiment; its device form was
+retired with the other settled A/B builds, this emulation documents the arithmetic) against FGTable's
 segment search (the count of interior breakpoints below x, f16_device.h bracket / oracle
 f16ref.c): a numpy float32 emulation of the device arithmetic over every float within 3000 ulps
 of each breakpoint, a million uniform samples and the infinities, for the alpha, beta13 and union

@@ -70,9 +70,24 @@ def main():
     analyse(lines, kernel, flags)
 
 
+def kernel_spans(lines):
+    """{kernel symbol: (index of its label, index of its .Lfunc_end)} of a device-assembly dump
+    (hipcc --cuda-device-only -S), in one pass; kernels are the symbols with an .amdhsa_kernel block."""
+    spans, label = {}, None
+    for i, l in enumerate(lines):
+        if l.startswith(".Lfunc_end"):
+            if label is not None and label[2]:
+                spans[label[0]] = (label[1], i)
+            label = None
+        elif label is not None and l.lstrip().startswith(".amdhsa_kernel "):
+            label[2] = True
+        elif l[:1] not in ("", "\t", " ", ".", ";") and l.split(";")[0].rstrip().endswith(":"):
+            label = [l.split(";")[0].rstrip()[:-1], i, False]  # (the latest global label: data objects have them too)
+    return spans
+
+
 def analyse(lines, kernel, flags):
-    start = next(i for i, l in enumerate(lines) if l.startswith(kernel + ":"))
-    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    start, end = kernel_spans(lines)[kernel]
     body = lines[start:end]
     meta = {}
     for l in lines[end:]:
