@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .abi import F16ENV_ABI_VERSION, EnvConfig, RolloutSlot
+from .abi import F16ENV_ABI_VERSION, EnvConfig, PolicyDesc, RolloutSlot
 
 LIB_PATH = os.environ.get("F16ENV_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libf16env.so")
 
@@ -82,6 +82,9 @@ def lib():
     _set(L, "f16env_bootstrap_stash", [vp, i64, i32, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64], i32)
     _set(L, "f16env_bootstrap_apply", [vp, i64, vp, vp, vp, ctypes.c_double], i32)
     _set(L, "f16env_abi_version", [], i32)
+    _set(L, "f16env_policy_blob_layout", [ctypes.POINTER(PolicyDesc), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32)
+    _set(L, "f16env_policy_forward", [vp, ctypes.POINTER(PolicyDesc), vp, i64, vp, i64, i64, u64, u64, i64, vp, vp, vp,
+                                      vp, ctypes.c_uint32], i32)
     L.f16env_set_state.argtypes = [vp, vp, vp]
     L.f16env_trim.argtypes = [vp, vp, vp, vp, vp]
     L.f16env_sample_actions.argtypes = [vp, vp, u64, u64, vp]
@@ -135,4 +138,5 @@ EXPORTED_SYMBOLS = (
     "f16env_get_state",
     "f16env_set_state", "f16env_trim", "f16env_sample_actions", "f16env_gae", "f16env_features", "f16env_poses", "f16env_step_kernel_name", "f16env_step_waves_per_simd", "f16env_step_variant", "f16env_profile_begin", "f16env_profile_end", "f16env_profile_times",
     "f16env_algorithmic_bytes_per_env_step", "f16env_last_error",
+    "f16env_policy_blob_layout", "f16env_policy_forward",
 )

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 
-F16ENV_ABI_VERSION = 6  # include/f16env.h (checked against f16env_abi_version() at load)
+F16ENV_ABI_VERSION = 7  # include/f16env.h (checked against f16env_abi_version() at load)
 F16_OBS_DIM = 15
 F16_ACT_DIM = 4
 
@@ -162,3 +162,70 @@ class RolloutSlot(ctypes.Structure):
         ("flags", ctypes.c_uint32),
         ("reserved", ctypes.c_uint32),
     ]
+
+
+# ABI 7: the device policy (f16env_policy_forward)
+F16_POLICY_ACT_TANH = 0
+F16_POLICY_ACT_RELU = 1
+F16_POLICY_DETERMINISTIC = 0x1  # eps = 0: the action is the mean
+F16_POLICY_VALUE_ONLY = 0x2     # the vf branch alone; actions / log_probs not touched
+F16_POLICY_N_OFFSETS = 17       # f16env_policy_blob_layout: 6 b + 2 l (+ 1) weight (bias) of layer l, branch b
+F16_POLICY_OFF_ACT_W, F16_POLICY_OFF_ACT_B, F16_POLICY_OFF_VAL_W, F16_POLICY_OFF_VAL_B = 12, 13, 14, 15
+F16_POLICY_OFF_LOG_STD = 16
+POLICY_WIDTHS = (32, 64, 96, 128)
+POLICY_MAX_LAYERS = 3
+
+
+class PolicyDesc(ctypes.Structure):
+    """f16_policy_desc (include/f16env.h): the shape of an actor-critic MLP policy."""
+    _fields_ = [
+        ("K", ctypes.c_int32),
+        ("D", ctypes.c_int32),
+        ("n_pi", ctypes.c_int32),
+        ("n_vf", ctypes.c_int32),
+        ("pi_width", ctypes.c_int32 * 3),
+        ("vf_width", ctypes.c_int32 * 3),
+        ("activation", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+def policy_desc(stack_k: int, frame_dim: int, pi_widths, vf_widths, activation="tanh") -> PolicyDesc:
+    acts = {"tanh": F16_POLICY_ACT_TANH, "relu": F16_POLICY_ACT_RELU}
+    if activation not in acts:
+        raise ValueError("activation must be 'tanh' or 'relu', got %r" % (activation,))
+    pi_widths, vf_widths = [int(w) for w in pi_widths], [int(w) for w in vf_widths]
+    if not 1 <= int(stack_k) <= 10 or int(frame_dim) not in (15, 17):
+        raise ValueError("stack_k must be in 1..10 and frame_dim 15 or 17")
+    for ws in (pi_widths, vf_widths):
+        if not 1 <= len(ws) <= POLICY_MAX_LAYERS or any(w not in POLICY_WIDTHS for w in ws):
+            raise ValueError("each branch has 1 to 3 hidden layers of width 32, 64, 96 or 128, got %s" % (ws,))
+    d = PolicyDesc()
+    d.K, d.D, d.n_pi, d.n_vf = int(stack_k), int(frame_dim), len(pi_widths), len(vf_widths)
+    for i, w in enumerate(pi_widths):
+        d.pi_width[i] = w
+    for i, w in enumerate(vf_widths):
+        d.vf_width[i] = w
+    d.activation = acts[activation]
+    return d
+
+
+def policy_blob_layout(d: PolicyDesc):
+    """Python twin of f16env_policy_blob_layout: (offsets[F16_POLICY_N_OFFSETS], n_floats)."""
+    off = [-1] * F16_POLICY_N_OFFSETS
+    p = 0
+    for heads in (False, True):  # the hidden layers of both branches, then the two heads (one tile each)
+        for b in range(2):
+            fan_in = d.K * d.D
+            widths = list(d.vf_width[:d.n_vf]) if b else list(d.pi_width[:d.n_pi])
+            for l, width in enumerate(widths + [32]):
+                head = l == len(widths)
+                if head == heads:
+                    slot = (F16_POLICY_OFF_VAL_W if b else F16_POLICY_OFF_ACT_W) if head else 6 * b + 2 * l
+                    off[slot] = p
+                    p += (width // 32) * ((fan_in + 1) // 2) * 64
+                    off[slot + 1] = p
+                    p += width
+                fan_in = width
+    off[F16_POLICY_OFF_LOG_STD] = p
+    return off, p + 4

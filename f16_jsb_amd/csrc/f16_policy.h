@@ -1,0 +1,386 @@
+// f16_policy.h -- the actor-critic MLP forward of a rollout as one HIP kernel (gfx950), and the
+// host side of f16env_policy_blob_layout / f16env_policy_forward (include/f16env.h, ABI 7).
+// Included by f16env.hip after its error handling and Philox (set_err, HIPCHK, philox).
+//
+// actions, values, log_probs = policy(obs) for stable_baselines3's ActorCriticPolicy with separate
+// pi / vf MLPs (common/policies.py:ActorCriticPolicy.forward, torch_layers.py:MlpExtractor, a
+// DiagGaussianDistribution with a state-independent log_std), float32 throughout.
+//
+// Tile: one wave owns 32 observation rows; a block is 4 waves (128 rows). Every layer is
+// H^T = W X^T on v_mfma_f32_32x32x2_f32 (an exact k-ordered f32 fma chain per output, so a row's
+// result does not depend on the rows beside it): the MFMA's rows are 32 hidden units, its columns
+// the wave's 32 observation rows.
+//   A operand (weights): lane l holds W[32 to + (l & 31)][2 s + (l >> 5)] for output tile `to`,
+//     k-step s -- the blob stores each layer in exactly that order, [to][s][64 lanes], so the
+//     operand is one coalesced 256-B read per MFMA (from LDS when the blob fits, else L2).
+//   B operand (activations): lane l holds X[2 s + (l >> 5)][l & 31] from the wave's own LDS image
+//     [k][row]; the observation is staged there once (stride 33, the 32 rows of a k contiguous),
+//     a layer's output replaces the hidden image in place (stride 32) after its last MFMA.
+//   C/D: lane l, register r of tile `to` = unit 32 to + (r & 3) + 8 (r >> 2) + 4 (l >> 5) of row l & 31;
+//     the bias is the accumulator's initial value, the activation runs on the registers.
+// The heads are layers of one tile (rows past 4 / 1 are zero weights); lanes 0..31 hold their
+// row's action mean in registers 0..3 and its value in register 0, and sample / store from there.
+#pragma once
+
+namespace f16 {
+
+typedef float pol_f32x16 __attribute__((ext_vector_type(16)));
+typedef float pol_f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int POL_WAVES = 4;           // waves (row tiles) per block
+constexpr int POL_ROWS = 32;           // rows per wave
+constexpr int POL_XS = 33;             // row stride of the staged observation image (floats)
+constexpr int POL_LDS_BYTES = 160 * 1024;
+constexpr int POL_MAX_LAYERS = 3;
+constexpr int POL_OPS = 2 * (POL_MAX_LAYERS + 1);  // pi layers, pi head, vf layers, vf head
+
+struct PolicyOp {
+  int32_t w_off, b_off;  // floats into the blob
+  int32_t nks;           // k-steps (pairs of inputs)
+  int32_t tout;          // output tiles of 32 units
+};
+struct PolicyArgs {
+  const float* blob;
+  const float* obs;
+  const float* eps;
+  float* actions;
+  float* values;
+  float* log_probs;
+  int64_t n, row_stride, frame_stride, id_base;
+  uint64_t seed, step;
+  int32_t K, in_dim, obs_floats, hid_floats, blob_floats, n_pi, n_vf, relu, flags, logstd_off;
+  PolicyOp ops[POL_OPS];
+};
+
+__device__ __forceinline__ int pol_unit(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// acc[to] = bias + W[to] X over nks k-steps (see the operand maps above)
+template <int TOUT>
+__device__ __forceinline__ void policy_gemm(const float* __restrict__ wb, const PolicyOp op, const float* xin,
+                                            const int xstride, const int lane, pol_f32x16 (&acc)[4]) {
+  const int j = lane & 31, h = lane >> 5;
+  const float* bias = wb + op.b_off;
+#pragma unroll
+  for (int to = 0; to < TOUT; ++to) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[to][r] = bias[32 * to + pol_unit(r, h)];
+  }
+  const float* xp = xin + h * xstride + j;
+  const float* wp = wb + op.w_off + lane;
+  const int nks = op.nks;
+  // batches of four k-steps; the next batch's operands are loaded ahead of this batch's MFMAs
+  // (the last batch re-reads itself: no branch, nothing out of bounds)
+  const int nb = nks >> 2;
+  float b[4], w[TOUT][4];
+  if (nb > 0) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      b[u] = xp[2 * u * xstride];
+#pragma unroll
+      for (int to = 0; to < TOUT; ++to) w[to][u] = wp[(to * nks + u) * 64];
+    }
+  }
+  for (int q = 0; q < nb; ++q) {
+    const int sn = 4 * (q + 1 < nb ? q + 1 : q);
+    float bn[4], wn[TOUT][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      bn[u] = xp[2 * (sn + u) * xstride];
+#pragma unroll
+      for (int to = 0; to < TOUT; ++to) wn[to][u] = wp[(to * nks + sn + u) * 64];
+    }
+    __builtin_amdgcn_sched_barrier(0);  // keep the loads a whole batch ahead (the scheduler sinks them otherwise)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+      for (int to = 0; to < TOUT; ++to) acc[to] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[to][u], b[u], acc[to], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      b[u] = bn[u];
+#pragma unroll
+      for (int to = 0; to < TOUT; ++to) w[to][u] = wn[to][u];
+    }
+  }
+  int s = 4 * nb;
+  for (; s < nks; ++s) {
+    const float b = xp[2 * s * xstride];
+#pragma unroll
+    for (int to = 0; to < TOUT; ++to)
+      acc[to] = __builtin_amdgcn_mfma_f32_32x32x2f32(wp[(to * nks + s) * 64], b, acc[to], 0, 0, 0);
+  }
+}
+
+// tanh(v) = sign(v) (1 - t) / (1 + t), t = exp(-2 |v|), on the hardware exp2 and reciprocal (about
+// 1 ulp each): absolute error <= ~2e-7 everywhere (the relative error grows below |v| ~ 0.1, where
+// 1 - t cancels), NaN passes, +-inf gives +-1. libm's tanhf, inlined 128 times per row, was the
+// largest single cost of the kernel.
+__device__ __forceinline__ float policy_tanh(const float v) {
+  const float t = __builtin_amdgcn_exp2f(-2.8853900817779268f * fabsf(v));  // 2 log2(e)
+  return copysignf((1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t), v);
+}
+
+// one hidden layer: the activation of the accumulators replaces the hidden image (stride 32)
+template <int TOUT>
+__device__ __forceinline__ void policy_hidden(const float* __restrict__ wb, const PolicyOp op, const float* xin,
+                                              const int xstride, float* hs, const int relu, const int lane,
+                                              pol_f32x16 (&acc)[4]) {
+  policy_gemm<TOUT>(wb, op, xin, xstride, lane, acc);
+  __builtin_amdgcn_wave_barrier();  // every read of the input image is ahead of the writes below
+  const int j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int to = 0; to < TOUT; ++to) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float v = acc[to][r];
+      hs[(32 * to + pol_unit(r, h)) * POL_ROWS + j] = relu ? (v < 0.0f ? 0.0f : v) : policy_tanh(v);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The policy's noise stream (include/f16env.h): Philox4x32-10 keyed by seed, counter
+// (gid, gid_hi ^ 'POLI', step), two Box-Muller pairs formed as rng_normals forms its own.
+__device__ __forceinline__ void policy_normals(uint64_t seed, uint64_t gid, uint64_t step, float* e) {
+  uint32_t o[4];
+  philox((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)gid, (uint32_t)(gid >> 32) ^ 0x504F4C49u, (uint32_t)step,
+         (uint32_t)(step >> 32), o);
+  const float s24 = 1.0f / 16777216.0f;
+  const float u1 = ((float)(o[0] >> 8) + 0.5f) * s24, u2 = (float)(o[1] >> 8) * s24;
+  const float u3 = ((float)(o[2] >> 8) + 0.5f) * s24, u4 = (float)(o[3] >> 8) * s24;
+  const float r1 = sqrtf(-2.0f * logf(u1)), r2 = sqrtf(-2.0f * logf(u3));
+  float s2, c2, s4, c4;
+  sincospif(2.0f * u2, &s2, &c2);
+  sincospif(2.0f * u4, &s4, &c4);
+  e[0] = r1 * c2;
+  e[1] = r1 * s2;
+  e[2] = r2 * c4;
+  e[3] = r2 * s4;
+}
+
+template <int D, bool WLDS>
+__global__ __launch_bounds__(64 * POL_WAVES) void f16_policy_forward_kernel(const PolicyArgs a) {
+  extern __shared__ float4 pol_sm4[];
+  float* sm = reinterpret_cast<float*>(pol_sm4);
+  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float* wb = a.blob;
+  if (WLDS) {  // the whole blob into LDS, shared by the block's waves
+    const pol_f32x4* src = reinterpret_cast<const pol_f32x4*>(a.blob);
+    pol_f32x4* dst = reinterpret_cast<pol_f32x4*>(pol_sm4);
+    const int n4 = a.blob_floats >> 2;
+    constexpr int NT = 64 * POL_WAVES, U = 8;  // eight 16-B loads in flight per thread, then their LDS writes
+    for (int i0 = tid; i0 < n4; i0 += NT * U) {
+      pol_f32x4 t[U];
+      // (indices past the end repeat the last element, load and write alike: no branch per element)
+#pragma unroll
+      for (int u = 0; u < U; ++u) t[u] = src[i0 + NT * u < n4 ? i0 + NT * u : n4 - 1];
+      __builtin_amdgcn_sched_barrier(0);  // all the loads issue before the first write waits for its own
+#pragma unroll
+      for (int u = 0; u < U; ++u) dst[i0 + NT * u < n4 ? i0 + NT * u : n4 - 1] = t[u];
+    }
+    __syncthreads();
+    wb = sm;
+  }
+  const int64_t row0 = ((int64_t)blockIdx.x * POL_WAVES + wave) * POL_ROWS;
+  if (row0 >= a.n) return;  // (after the block's only barrier)
+  float* xs = sm + (WLDS ? a.blob_floats : 0) + wave * (a.obs_floats + a.hid_floats);
+  float* hs = xs + a.obs_floats;
+  const int j = lane & 31, h = lane >> 5;
+
+  // the wave's 32 rows, flattened (K, D) each, into xs[k * D + d][row]; rows past n - 1 repeat it
+  // (two frames' loads in flight, then their LDS writes; indices past the end repeat the last
+  // element or frame, load and write alike: no branch per element)
+  constexpr int NE = (POL_ROWS * D + 63) / 64;
+  for (int k0 = 0; k0 < a.K; k0 += 2) {
+    float v[2][NE];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const float* fk = a.obs + (int64_t)(k0 + kk < a.K ? k0 + kk : a.K - 1) * a.frame_stride;
+#pragma unroll
+      for (int i = 0; i < NE; ++i) {
+        const int e0 = lane + 64 * i, e = e0 < POL_ROWS * D ? e0 : POL_ROWS * D - 1, rj = e / D, d = e - rj * D;
+        int64_t row = row0 + rj;
+        row = row < a.n ? row : a.n - 1;
+        v[kk][i] = fk[row * a.row_stride + d];  // (always a valid element: no branch per load)
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+      for (int i = 0; i < NE; ++i) {
+        const int e0 = lane + 64 * i, e = e0 < POL_ROWS * D ? e0 : POL_ROWS * D - 1, rj = e / D, d = e - rj * D;
+        xs[((k0 + kk < a.K ? k0 + kk : a.K - 1) * D + d) * POL_XS + rj] = v[kk][i];
+      }
+    }
+  }
+  if ((a.in_dim & 1) && lane < POL_ROWS) xs[a.in_dim * POL_XS + lane] = 0.0f;  // the zero-weight pad input
+  __builtin_amdgcn_wave_barrier();
+
+  pol_f32x16 acc[4];
+  float mean[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  float value = 0.0f;
+  for (int br = (a.flags & F16_POLICY_VALUE_ONLY) ? 1 : 0; br < 2; ++br) {
+    const int base = br * (POL_MAX_LAYERS + 1);
+    const int nl = br ? a.n_vf : a.n_pi;
+    const float* xin = xs;
+    int xstride = POL_XS;
+    for (int l = 0; l < nl; ++l) {
+      const PolicyOp op = a.ops[base + l];
+      switch (op.tout) {
+        case 1: policy_hidden<1>(wb, op, xin, xstride, hs, a.relu, lane, acc); break;
+        case 2: policy_hidden<2>(wb, op, xin, xstride, hs, a.relu, lane, acc); break;
+        case 3: policy_hidden<3>(wb, op, xin, xstride, hs, a.relu, lane, acc); break;
+        default: policy_hidden<4>(wb, op, xin, xstride, hs, a.relu, lane, acc); break;
+      }
+      xin = hs;
+      xstride = POL_ROWS;
+    }
+    policy_gemm<1>(wb, a.ops[base + POL_MAX_LAYERS], xin, xstride, lane, acc);
+    __builtin_amdgcn_wave_barrier();
+    if (br == 0) {
+      mean[0] = acc[0][0]; mean[1] = acc[0][1]; mean[2] = acc[0][2]; mean[3] = acc[0][3];
+    } else {
+      value = acc[0][0];
+    }
+  }
+
+  const int64_t row = row0 + j;
+  if (h != 0 || row >= a.n) return;
+  a.values[row] = value;
+  if (a.flags & F16_POLICY_VALUE_ONLY) return;
+  float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (!(a.flags & F16_POLICY_DETERMINISTIC)) {
+    if (a.eps) {
+      const float4 ev = reinterpret_cast<const float4*>(a.eps)[row];
+      e[0] = ev.x; e[1] = ev.y; e[2] = ev.z; e[3] = ev.w;
+    } else {
+      policy_normals(a.seed, (uint64_t)(a.id_base + row), a.step, e);
+    }
+  }
+  const float4 ls = *reinterpret_cast<const float4*>(wb + a.logstd_off);
+  const float lsv[4] = {ls.x, ls.y, ls.z, ls.w};
+  float av[4], lp = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    av[c] = mean[c] + expf(lsv[c]) * e[c];
+    lp += -0.5f * e[c] * e[c] - lsv[c] - 0.91893853320467274f;  // 0.5 log(2 pi)
+  }
+  reinterpret_cast<float4*>(a.actions)[row] = make_float4(av[0], av[1], av[2], av[3]);
+  a.log_probs[row] = lp;
+}
+
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+static const char* policy_desc_error(const f16_policy_desc* d) {
+  if (!d) return "null policy descriptor";
+  if (d->K < 1 || d->K > 10) return "policy K must be in [1, 10]";
+  if (d->D != 15 && d->D != 17) return "policy D must be 15 (frames) or 17 (features)";
+  if (d->n_pi < 1 || d->n_pi > POL_MAX_LAYERS || d->n_vf < 1 || d->n_vf > POL_MAX_LAYERS)
+    return "each policy branch has 1 to 3 hidden layers";
+  for (int b = 0; b < 2; ++b)
+    for (int l = 0; l < (b ? d->n_vf : d->n_pi); ++l) {
+      const int w = b ? d->vf_width[l] : d->pi_width[l];
+      if (w != 32 && w != 64 && w != 96 && w != 128) return "hidden widths must be 32, 64, 96 or 128";
+    }
+  if (d->activation != F16_POLICY_ACT_TANH && d->activation != F16_POLICY_ACT_RELU)
+    return "policy activation must be F16_POLICY_ACT_TANH or F16_POLICY_ACT_RELU";
+  return nullptr;
+}
+
+// The blob: per branch (pi, then vf) each hidden layer's weight as [tiles of 32 outputs][k-steps][2][32]
+// (element = W[32 to + i][2 s + h], inputs past the layer's fan-in zero) then its bias; then the
+// action head and the value head in the same form as one tile each (outputs past 4 / 1 zero, a bias of
+// 32); then log_std[4]. Every piece starts on a multiple of 4 floats.
+static int64_t policy_layout(const f16_policy_desc* d, int64_t* off, PolicyOp* ops) {
+  int64_t p = 0;
+  for (int i = 0; i < F16_POLICY_N_OFFSETS; ++i) off[i] = -1;
+  for (int pass = 0; pass < 2; ++pass) {  // the hidden layers of both branches, then the two heads
+    for (int b = 0; b < 2; ++b) {
+      int fan_in = d->K * d->D;
+      const int nl = b ? d->n_vf : d->n_pi;
+      for (int l = 0; l <= nl; ++l) {  // l == nl: the branch's head
+        const bool head = l == nl;
+        const int width = head ? 32 : (b ? d->vf_width[l] : d->pi_width[l]);
+        if (head == (pass == 1)) {
+          const int nks = (fan_in + 1) / 2, tout = width / 32;
+          const int slot = head ? (b ? F16_POLICY_OFF_VAL_W : F16_POLICY_OFF_ACT_W) : 6 * b + 2 * l;
+          off[slot] = p;
+          p += (int64_t)tout * nks * 64;
+          off[slot + 1] = p;
+          p += width;
+          if (ops) {
+            PolicyOp& o = ops[b * (POL_MAX_LAYERS + 1) + (head ? POL_MAX_LAYERS : l)];
+            o.w_off = (int32_t)off[slot]; o.b_off = (int32_t)off[slot + 1]; o.nks = nks; o.tout = tout;
+          }
+        }
+        fan_in = width;
+      }
+    }
+  }
+  off[F16_POLICY_OFF_LOG_STD] = p;
+  return p + 4;
+}
+
+static int policy_forward_impl(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
+                               int64_t row_stride, int64_t frame_stride, uint64_t seed, uint64_t step, int64_t id_base,
+                               const float* eps, float* actions, float* values, float* log_probs, uint32_t flags) {
+  if (const char* m = policy_desc_error(desc)) return set_err(-1, m);
+  if (flags & ~(uint32_t)(F16_POLICY_DETERMINISTIC | F16_POLICY_VALUE_ONLY)) return set_err(-1, "unknown f16env_policy_forward flags");
+  if (n < 0) return set_err(-1, "n must be >= 0");
+  const bool vonly = (flags & F16_POLICY_VALUE_ONLY) != 0;
+  PolicyArgs a{};
+  int64_t off[F16_POLICY_N_OFFSETS];
+  const int64_t nf = policy_layout(desc, off, a.ops);
+  int max_w = 32;
+  for (int l = 0; l < desc->n_pi; ++l) max_w = desc->pi_width[l] > max_w ? desc->pi_width[l] : max_w;
+  for (int l = 0; l < desc->n_vf; ++l) max_w = desc->vf_width[l] > max_w ? desc->vf_width[l] : max_w;
+  a.K = desc->K;
+  a.in_dim = desc->K * desc->D;
+  a.obs_floats = (a.in_dim + (a.in_dim & 1)) * POL_XS;
+  a.hid_floats = max_w * POL_ROWS;
+  a.blob_floats = (int32_t)nf;
+  const int64_t tiles = (int64_t)POL_WAVES * (a.obs_floats + a.hid_floats) * 4;
+  const bool wlds = nf * 4 + tiles <= POL_LDS_BYTES;
+  const int64_t lds = tiles + (wlds ? nf * 4 : 0);
+  const void* fn = desc->D == 15
+      ? (wlds ? (const void*)f16_policy_forward_kernel<15, true> : (const void*)f16_policy_forward_kernel<15, false>)
+      : (wlds ? (const void*)f16_policy_forward_kernel<17, true> : (const void*)f16_policy_forward_kernel<17, false>);
+  if (n > 0) {
+    if (!blob || !obs || !values || (!vonly && (!actions || !log_probs))) return set_err(-1, "null argument");
+    if (((uintptr_t)blob & 15) != 0) return set_err(-1, "the weight blob must be 16-byte aligned");
+    if (((uintptr_t)obs & 3) != 0 || ((uintptr_t)values & 3) != 0 || ((uintptr_t)log_probs & 3) != 0)
+      return set_err(-1, "obs, values and log_probs must be float-aligned");
+    if (!vonly && (((uintptr_t)actions & 15) != 0 || ((uintptr_t)eps & 15) != 0))
+      return set_err(-1, "actions and eps must be 16-byte aligned");
+    if (row_stride < 0 || frame_stride < 0) return set_err(-1, "strides must be non-negative");
+  }
+  const int64_t blocks = (n + POL_WAVES * POL_ROWS - 1) / (POL_WAVES * POL_ROWS);
+  if (blocks > 0x7fffffffLL) return set_err(-1, "n too large");
+  // more than 64 KB of dynamic LDS is opted into once per kernel instance and device (n == 0
+  // does only this: a caller about to capture a graph prepares the instance ahead of it)
+  static uint64_t prepared[4];
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  const int inst = (desc->D == 17 ? 2 : 0) + (wlds ? 1 : 0);
+  if (dev < 0 || dev >= 64 || !(__atomic_load_n(&prepared[inst], __ATOMIC_ACQUIRE) >> dev & 1)) {
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_BYTES));
+    if (dev >= 0 && dev < 64) __atomic_fetch_or(&prepared[inst], 1ull << dev, __ATOMIC_RELEASE);
+  }
+  if (n == 0) return 0;
+  a.blob = blob; a.obs = obs; a.eps = vonly ? nullptr : eps;
+  a.actions = actions; a.values = values; a.log_probs = log_probs;
+  a.n = n; a.row_stride = row_stride; a.frame_stride = frame_stride; a.id_base = id_base;
+  a.seed = seed; a.step = step;
+  a.n_pi = desc->n_pi; a.n_vf = desc->n_vf;
+  a.relu = desc->activation == F16_POLICY_ACT_RELU ? 1 : 0;
+  a.flags = (int32_t)flags;
+  a.logstd_off = (int32_t)off[F16_POLICY_OFF_LOG_STD];
+  void* kargs[] = {&a};
+  HIPCHK(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * POL_WAVES), kargs, (size_t)lds, (hipStream_t)stream));
+  return 0;
+}
+
+}  // namespace f16

@@ -2477,6 +2477,8 @@ static EnvArgs env_args(const f16env* h) {
   return E;
 }
 
+#include "f16_policy.h"
+
 extern "C" {
 
 int f16env_config_default(f16env_config* c) {
@@ -3386,6 +3388,20 @@ int f16env_gae(void* stream, int64_t n_steps, int64_t n_envs, const float* rewar
                      episode_starts, last_values, dones, g, gl, advantages, returns);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+int f16env_policy_blob_layout(const f16_policy_desc* desc, int64_t* offsets_out, int64_t* n_floats_out) {
+  if (const char* m = policy_desc_error(desc)) return set_err(-1, m);
+  if (!offsets_out || !n_floats_out) return set_err(-1, "null argument");
+  *n_floats_out = policy_layout(desc, offsets_out, nullptr);
+  return 0;
+}
+
+int f16env_policy_forward(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
+                          int64_t row_stride, int64_t frame_stride, uint64_t seed, uint64_t step, int64_t id_base,
+                          const float* eps, float* actions, float* values, float* log_probs, uint32_t flags) {
+  return policy_forward_impl(stream, desc, blob, n, obs, row_stride, frame_stride, seed, step, id_base, eps, actions,
+                             values, log_probs, flags);
 }
 
 int f16env_features(void* stream, int64_t n_frames, const float* obs, float* feat) {

@@ -121,6 +121,10 @@ def collect_rollout(envs, buf: DeviceRolloutBuffer, seed: int = 0, step0: int = 
     values when given, else policy_fn's values; last_values = V(final obs).
     policy_fn None: the uniform random policy from the device Philox stream (seed, step0 + t),
     values and log-probs zero, no bootstrap.
+    policy_fn a DevicePolicy (f16_jsb_amd.policy): the fused path calls its kernel with
+    step = step0 + t and the buffer's own rows as outputs (values[t], log_probs[t]; the actions
+    through one reused (N, 4) scratch the step's slot reads), and value_fn defaults to its
+    .value -- bit-identical to the same policy driven through a closure on the generic path.
 
     fused: each step is ONE launch (f16env_step_rollout / f16env_window_step_rollout) that takes
     (or draws) the actions and writes the slot's actions / rewards / next episode starts and one
@@ -153,6 +157,10 @@ def collect_rollout(envs, buf: DeviceRolloutBuffer, seed: int = 0, step0: int = 
         starts = torch.ones(n, dtype=torch.float32, device=dev)
     buf.reset()
     window = bool(getattr(envs, "window", False))
+    from .policy import DevicePolicy
+    device_policy = isinstance(policy_fn, DevicePolicy)
+    if device_policy and value_fn is None:
+        value_fn = policy_fn.value
     vfn = value_fn if value_fn is not None else (lambda o: policy_fn(o)[1])
     use_fused = fused and hasattr(envs, "step_rollout") and buf.actions.data_ptr() % 16 == 0 \
         and (window or (buf.frames[0].data_ptr() % 16 == 0 and (n * F16_OBS_DIM * 4) % 16 == 0))
@@ -201,9 +209,17 @@ def collect_rollout(envs, buf: DeviceRolloutBuffer, seed: int = 0, step0: int = 
             stash_idx = torch.empty(cap, dtype=torch.int64, device=dev)
             stash_n = torch.zeros(1, dtype=torch.int32, device=dev)
             stash_fn = L.f16env_bootstrap_stash
+        # a DevicePolicy writes values / log-probs straight into the buffer's rows and its actions
+        # into one reused scratch the step's slot reads: no per-step copies or shape fix-ups
+        device_policy = device_policy and raw
+        if device_policy:
+            act_scratch = torch.empty((n, 4), dtype=torch.float32, device=dev)
         for t in range(T):
             act_ptr = None
-            if policy_fn is not None:
+            if device_policy:
+                policy_fn.forward_into(obs, int(step0) + t, act_scratch, buf.values[t], buf.log_probs[t])
+                act_ptr = act_scratch.data_ptr()
+            elif policy_fn is not None:
                 act, v, lp = policy_fn(obs)
                 if not (act.dtype == torch.float32 and act.is_contiguous() and act.shape == (n, 4)
                         and act.device == dev and act.data_ptr() % 16 == 0):

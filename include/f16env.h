@@ -30,6 +30,9 @@
  *   f16env_bootstrap_stash / f16env_bootstrap_apply <- the same, deferred to the end of the
  *                      rollout (one value evaluation over the stashed terminal observations)
  *   f16env_gae      <- stable_baselines3/common/buffers.py:403-438 (device rollout, 8f rank 1)
+ *   f16env_policy_forward <- on_policy_algorithm.py:199-202 policy(obs_tensor): common/policies.py
+ *                      ActorCriticPolicy.forward with torch_layers.py MlpExtractor's separate pi / vf
+ *                      MLPs and a DiagGaussianDistribution, one launch
  *   f16env_features <- jsbsim_gym/features.py:37-67 JSBSimFeatureExtractor.forward (8f rank 3)
  *   f16env_features_window_step <- the same per step on a windowed observation, one frame each
  *   f16env_poses    <- jsbsim_gym.py:381-415 JSBSimEnv.render state -> Viewer poses (8f rank 4)
@@ -54,8 +57,10 @@ extern "C" {
  * f16env_window_step_ex_kernel_name; nothing else changed.
  * 5 (round 5): new F16_STEP_POSES flag and f16env_window_poses_bind; nothing else changed.
  * 6 (round 6): new f16env_sample_actions_steps and f16env_window_resets_deferred; nothing else
- * changed. */
-#define F16ENV_ABI_VERSION 6
+ * changed.
+ * 7: new f16_policy_desc, f16env_policy_blob_layout and f16env_policy_forward (the actor-critic
+ * MLP forward of a rollout as one kernel); nothing else changed. */
+#define F16ENV_ABI_VERSION 7
 
 /* Frame layout (jsbsim_gym.py:12-25 STATE_FORMAT + goal, :172-197) */
 #define F16_OBS_DIM 15
@@ -460,6 +465,73 @@ int f16env_sample_actions_steps(f16env_t h, void* stream, uint64_t seed, uint64_
 int f16env_gae(void* stream, int64_t n_steps, int64_t n_envs, const float* rewards, const float* values,
                const float* episode_starts, const float* last_values, const uint8_t* dones, double gamma,
                double gae_lambda, float* advantages, float* returns);
+
+/* ABI 7. The policy of a rollout on the device: actions, values, log_probs = policy(obs) for
+ * stable_baselines3's ActorCriticPolicy with separate pi / vf MLPs (policies.py
+ * ActorCriticPolicy.forward; MlpExtractor; DiagGaussianDistribution with a state-independent
+ * log_std), float32 inputs, weights and accumulation (the f32-input MFMA: per output an exact
+ * k-ordered fmaf chain starting from the bias, so a row's result does not depend on the batch it
+ * is evaluated in). The feature extractor is the flattening of the (K, D) stack.
+ *   K, D         frames per observation (1..10) and floats per frame: 15 (observation frames) or 17
+ *                (f16env_features frames); the network's input is the K*D flattened stack
+ *   n_pi, n_vf   hidden layers per branch (1..3); pi_width / vf_width their widths (32, 64, 96, 128)
+ *   activation   F16_POLICY_ACT_TANH or F16_POLICY_ACT_RELU after every hidden layer (tanh as
+ *                sign(v) (1 - t) / (1 + t), t = exp(-2|v|): absolute error about 2e-7 at most)
+ * The action head is (last pi width) -> 4, the value head (last vf width) -> 1. */
+#define F16_POLICY_ACT_TANH 0
+#define F16_POLICY_ACT_RELU 1
+typedef struct f16_policy_desc {
+  int32_t K, D;
+  int32_t n_pi, n_vf;
+  int32_t pi_width[3];
+  int32_t vf_width[3];
+  int32_t activation;
+  int32_t reserved;
+} f16_policy_desc;
+
+/* The packed weight blob the kernel reads (pure host function, no device): offsets_out receives
+ * F16_POLICY_N_OFFSETS offsets in floats (-1: the layer does not exist), *n_floats_out the
+ * blob's length. Offsets 6 b + 2 l / 6 b + 2 l + 1: weight / bias of hidden layer l of branch b
+ * (0 pi, 1 vf); then the heads and log_std by the names below. Every offset is a multiple of 4
+ * floats; the blob itself must be 16-B aligned.
+ *   weight of a layer with `out` outputs and `in` inputs (torch's W[out][in]): out/32 tiles x
+ *     ceil(in/2) k-steps x 64 floats, element [to][s][h][i] = W[32 to + i][2 s + h] (h = 0, 1;
+ *     i = 0..31), zero where 2 s + h >= in (an odd fan-in is padded in the weights, not in memory)
+ *   bias: `out` floats
+ *   heads: the same form as ONE tile (outputs past the head's 4 / 1 are zero weights), bias 32
+ *     floats (zero past 4 / 1)
+ *   log_std: 4 floats. */
+#define F16_POLICY_N_OFFSETS 17
+#define F16_POLICY_OFF_ACT_W 12
+#define F16_POLICY_OFF_ACT_B 13
+#define F16_POLICY_OFF_VAL_W 14
+#define F16_POLICY_OFF_VAL_B 15
+#define F16_POLICY_OFF_LOG_STD 16
+int f16env_policy_blob_layout(const f16_policy_desc* desc, int64_t* offsets_out, int64_t* n_floats_out);
+
+/* One launch: row b of the batch is the flattened (K, D) stack at obs + b*row_stride +
+ * k*frame_stride (floats, non-negative strides, as f16env_features_strided: a windowed
+ * observation in place, a contiguous (n, K, 15) block, the (n, K, 17) feature window).
+ *   mean = action head(pi MLP(x)), values = value head(vf MLP(x))           (n float)
+ *   actions = mean + exp(log_std) * eps                                     (n x 4 float, 16-B aligned)
+ *   log_probs = sum_j (-0.5 eps_j^2 - log_std_j - 0.5 log 2 pi)             (n float)
+ * eps: the caller's n x 4 float (16-B aligned) when non-NULL, else drawn in the kernel from the
+ * POLICY NOISE stream: o = Philox4x32-10 keyed by `seed`, counter (gid, gid_hi ^ 0x504F4C49,
+ * step, step_hi), gid = id_base + b; two Box-Muller pairs as the gust stream forms its own
+ * (fp32): u1 = ((o0 >> 8) + 0.5) 2^-24, u2 = (o1 >> 8) 2^-24, r = sqrtf(-2 logf(u1)),
+ * eps0 = r cospi(2 u2), eps1 = r sinpi(2 u2); eps2, eps3 the same from o2, o3. A shard that
+ * passes its env_id_base draws the rows of the single run.
+ * flags  F16_POLICY_DETERMINISTIC: eps = 0 (the action is the mean; log_probs that of eps = 0);
+ *        F16_POLICY_VALUE_ONLY: the vf branch alone; actions, log_probs and eps are not touched and
+ *        may be NULL.
+ * Nothing outside rows [0, n) of any argument is read or written. No handle; stream-ordered; no
+ * sync and no allocation (safe under stream capture; n == 0 launches nothing and only prepares the
+ * kernel instance for the descriptor). A bad argument returns < 0 before any launch. */
+#define F16_POLICY_DETERMINISTIC 0x1
+#define F16_POLICY_VALUE_ONLY 0x2
+int f16env_policy_forward(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
+                          int64_t row_stride, int64_t frame_stride, uint64_t seed, uint64_t step, int64_t id_base,
+                          const float* eps, float* actions, float* values, float* log_probs, uint32_t flags);
 
 /* Policy features of every observation frame, replacing
  * jsbsim_gym/features.py:37-67 JSBSimFeatureExtractor.forward (float32):
