@@ -294,13 +294,56 @@ __device__ __forceinline__ float norm_angle(float a) {
   if (x == 0.0) x = 0.0;
   return (float)x;
 }
+// The observation's three angles: euler() and norm_angle() with their tests taken together.
+// euler() has two gimbal tests and each norm_angle four (NaN / Inf, the fmod guard, < 0, >= pi,
+// in fp64): as exec-mask branches each waits on its compare, on one wave's serial path, and
+// they keep three copies of OCML's fmod and two of atan2f between the hot blocks. norm_angle
+// is the identity on an ordinary angle (f16_device.h ANGLE_ORD_*), and on a heading that
+// euler() wrapped by 2*PI_F it is one fp64 subtraction: x >= pi there, and past 2*pi its fmod
+// is that same (exact) subtraction. So one wave-uniform test: a wave with every lane off the
+// gimbal poles and all three polynomial results ordinary runs straight-line code, any other
+// wave runs euler() and norm_angle() as they are, for all its lanes. The same bits either way.
+// The two-waves-per-SIMD (256-register) builds keep euler() + norm_angle() and the branching
+// env_reward below: three of them grew 4 to 8 B of scratch with the new forms (FAST = false at
+// their call sites). -DF16_ENV_LAYER_REF builds those earlier forms into every kernel from the
+// same source, for tests/test_gpu_env_layer.py and same-box A/Bs.
+#ifdef F16_ENV_LAYER_REF
+constexpr bool ENV_LAYER_FAST = false;
+#else
+constexpr bool ENV_LAYER_FAST = true;
+#endif
+__device__ __forceinline__ bool angle_ordinary(float a) {
+  const float m = fabsf(a);
+  return m >= ANGLE_ORD_MIN && m < ANGLE_ORD_END;  // (false for NaN / Inf)
+}
+template <bool FAST>
+__device__ __forceinline__ void euler_norm(const float* T, float* f) {
+  if constexpr (FAST && ENV_LAYER_FAST) {
+    const float tht = fatan2<true>(-T[2], fsqrt(__builtin_fmaf(T[5], T[5], T[8] * T[8])));  // as euler()
+    const float phi = fatan2<true>(T[5], T[8]);
+    const float p = fatan2<true>(T[1], T[0]);
+    const bool ord = (fabsf(T[2]) < 1.0f) & angle_ordinary(phi) & angle_ordinary(tht) & angle_ordinary(p);
+    if (__builtin_expect(__ballot(!ord) == 0ull, 1)) {
+      f[0] = phi; f[1] = tht;
+      f[2] = (p < 0.0f) ? (float)((double)(p + 2.0f * PI_F) - 2.0 * PI_D) : p;
+      return;
+    }
+  }
+  float phi, tht, psi;
+  euler(T, phi, tht, psi);
+  f[0] = norm_angle(phi); f[1] = norm_angle(tht); f[2] = norm_angle(psi);
+}
 // _get_current_single_observation (jsbsim_gym.py:172-197)
 // The observation frame (jsbsim_gym.py:172-197) from the derived quantities of the lane's
 // state; the latitude / longitude are evaluated here. (Reusing the last FDM frame's Derived
 // instead -- the frame's accelerations do not move rI, vI, q, wI -- saved 0.7 us per step at
 // 4 096 envs and nothing at 65 536 in the windowed step, r02_variants_keep.json, but the
 // two builds then round the observation differently: kept out, the one- and two-waves-per-
-// SIMD builds stay bit-identical.)
+// SIMD builds stay bit-identical. Round 8 tried it again in the one-wave builds only, frame()
+// handing out its Derived: bit-identical now that derive's products are explicit FMAs, but
+// carrying Tl2b and h_ft through the last frame put 128 B of scratch into every one-wave step
+// kernel, +1.26 us per step at 65 536 envs, profiles/r08_ab_env_layer.json "s3": kept out.)
+template <bool FAST = true>
 __device__ void make_frame_from(const Lane& L, double ce, double se, const Derived& d, float* f) {
   // explicit FMAs: with contraction left to the compiler, the one- and two-waves-per-SIMD
   // windowed builds paired these products differently, and yE (a difference of two ~2e7 ft
@@ -312,8 +355,6 @@ __device__ void make_frame_from(const Lane& L, double ce, double se, const Deriv
   const float rxyE = fsqrt(__builtin_fmaf(xf, xf, yf * yf));
   const float lat = atan2f(zf, rxyE);
   const float lon = (rxyE == 0.0f) ? 0.0f : atan2f(yf, xf);
-  float phi, tht, psi;
-  euler(d.Tl2b, phi, tht, psi);
   f[0] = (float)((double)lat * 6.3781e6);
   f[1] = (float)((double)lon * 6.3781e6);
   f[2] = (float)(d.h_ft * 0.3048);
@@ -321,13 +362,14 @@ __device__ void make_frame_from(const Lane& L, double ce, double se, const Deriv
   f[4] = L.lx[F16L_ALPHA];
   f[5] = L.lx[F16L_BETA];
   f[6] = d.pqr[0]; f[7] = d.pqr[1]; f[8] = d.pqr[2];
-  f[9] = norm_angle(phi); f[10] = norm_angle(tht); f[11] = norm_angle(psi);
+  euler_norm<FAST>(d.Tl2b, f + 9);
   f[12] = L.goal[0]; f[13] = L.goal[1]; f[14] = L.goal[2];
 }
+template <bool FAST = true>
 __device__ void make_frame(const Lane& L, double ce, double se, const AltRef& A, float* f) {
   Derived d;
   derive(L, ce, se, A, d);
-  make_frame_from(L, ce, se, d, f);
+  make_frame_from<FAST>(L, ce, se, d, f);
 }
 __device__ __forceinline__ float norm3f(float a, float b, float c) {
 #pragma clang fp contract(off)
@@ -367,7 +409,46 @@ struct EnvArgs {
 // the new frame f; Monitor's return (monitor.py:96-99). Returns the flags: bit 0 terminated,
 // 1 truncated, 2 quarantined by F16_FLAG_NAN_GUARD (a non-finite position / Mach / alpha /
 // beta / body rate; the angles f[9..11] are already NaN -> 0 by normalize_angle_mpi_pi).
-__device__ __forceinline__ int env_reward(Lane& L, const float* f, const EnvArgs& E, float& r32) {
+// Branch-free: crash / goal / truncation as selects over the same float32 operations in the same
+// order (the IEEE sqrtf of the goal test now runs for a crashed lane too, its result unused), and
+// the NaN guard as one wave-uniform arm that puts a quarantined lane's results back.
+__device__ __forceinline__ int env_reward_sel(Lane& L, const float* f, const EnvArgs& E, float& r32) {
+#pragma clang fp contract(off)
+  const float alt = f[2];
+  const bool crash = alt < E.crash;
+  const float dx = f[0] - f[12], dy = f[1] - f[13];
+  float d2 = dx * dx;
+  d2 = d2 + dy * dy;
+  const bool goal = !crash & (sqrtf(d2) < E.dg) & (fabsf(alt - f[14]) < E.dg);
+  double r = crash ? -10.0 : (goal ? 10.0 : 0.0);
+  int te = (crash | goal) ? 1 : 0;
+  int tr = L.step >= E.max_steps ? 1 : 0;                 // env :260 | TimeLimit
+  // (the previous distance in a register of its own: see the reference form below)
+  float last_d = L.last_d;
+  asm volatile("" : "+v"(last_d));
+  float dcur = norm3f(f[12] - f[0], f[13] - f[1], f[14] - f[2]);
+  const float ddiff = last_d - dcur;
+  r = r + E.gain * (double)ddiff;
+  double ret = L.ep_ret + r;                              // monitor.py:96-99
+  r32 = (float)r;
+  if (E.flags & F16_FLAG_NAN_GUARD) {
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) bad = bad | !isfinite(f[j]);
+    if (__ballot(bad) != 0ull) {  // terminated + quarantined (bit 2), reported as terminated[i] = 3
+      te = bad ? 5 : te;
+      tr = bad ? 0 : tr;
+      r32 = bad ? 0.0f : r32;
+      dcur = bad ? last_d : dcur;  // (the lane's last distance and return stay as they were)
+      ret = bad ? L.ep_ret : ret;
+    }
+  }
+  L.last_d = dcur;
+  L.ep_ret = ret;
+  return te | (tr << 1);
+}
+// (the form before it)
+__device__ __forceinline__ int env_reward_ref(Lane& L, const float* f, const EnvArgs& E, float& r32) {
   int te = 0, tr;
   bool bad = false;
   if (E.flags & F16_FLAG_NAN_GUARD) {
@@ -405,6 +486,11 @@ __device__ __forceinline__ int env_reward(Lane& L, const float* f, const EnvArgs
     r32 = (float)r;
   }
   return te | (tr << 1);
+}
+template <bool FAST = true>
+__device__ __forceinline__ int env_reward(Lane& L, const float* f, const EnvArgs& E, float& r32) {
+  if constexpr (FAST && ENV_LAYER_FAST) return env_reward_sel(L, f, E, r32);
+  return env_reward_ref(L, f, E, r32);
 }
 
 // reset a lane and produce its frame 0: the IC template copy (default config), or the full
@@ -475,7 +561,7 @@ __device__ void lane_reset_mode(Lane& L, const EnvArgs& E, int64_t k, const floa
   L.step = 0;
   L.ep_ret = 0.0;
   L.flags |= LANE_FLAG_FRESH;
-  make_frame(L, 1.0, 0.0, alt_ref(L, 1.0, 0.0), f0);
+  make_frame<!LOWREG>(L, 1.0, 0.0, alt_ref(L, 1.0, 0.0), f0);
   L.last_d = norm3f(f0[12] - f0[0], f0[13] - f0[1], f0[14] - f0[2]);
 }
 
@@ -1090,11 +1176,11 @@ __device__ __forceinline__ void step_body(const StepArgs& a, float* sT_lds, floa
     if (live) lane_store<GUST, 1, NT>(a.s, k, L);
   }
   if (live) {
-    make_frame(L, ce, se, A, f);  // :234
+    make_frame<!LOWREG>(L, ce, se, A, f);  // :234
     F16_STAMP(stamps, ST_FRAME_OBS);
     // reward / termination (:237-261), PositionReward (:493-507)
     float r32;
-    flags_out = env_reward(L, f, a.E, r32);  // bit 0 terminated, 1 truncated, 2 quarantined
+    flags_out = env_reward<!LOWREG>(L, f, a.E, r32);  // bit 0 terminated, 1 truncated, 2 quarantined
     F16_STAMP(stamps, ST_REWARD);
     done = flags_out & 3;
     rew_out = r32;
@@ -1655,9 +1741,9 @@ __global__ __launch_bounds__(BLOCK, OCC) void f16_rollout_kernel(RollArgs a) {
     for (int s = 0; s < a.E.down_sample; ++s)
       frame<OCC == 2, GUST>(L, cmd, ce, se, A, sT, a.C, false F16_STAMP_PASS);  // :225-232
     float f[F16_OBS_DIM];
-    make_frame(L, ce, se, A, f);                              // :234
+    make_frame<OCC != 2>(L, ce, se, A, f);                    // :234
     float r32;
-    const int fl = env_reward(L, f, a.E, r32);
+    const int fl = env_reward<OCC != 2>(L, f, a.E, r32);
     const int done = fl & 3;
     if (a.E.flags & F16_FLAG_NAN_GUARD) {
       const unsigned long long qm = __ballot(fl & 4);

@@ -2,12 +2,16 @@
 """Where the frame loop's VALU instructions come from (cross-compiled here, no GPU needed).
 
     python tools/isa_lines.py [-DFLAG ...] [--kernel MANGLED_NAME] [--top 40]
+    python tools/isa_lines.py --outside [--min-valu 8] [-DFLAG ...]   # the code around the loop
 
 Compiles the device code with the product library's flags plus -gline-tables-only (line tables
 do not change code generation), finds the kernel's FDM frame loop (the innermost loop with
 800-1000 VALU instructions, as tools/isa_stats.py reports it) and attributes each VALU
 instruction to the source line of its `.loc` directive (the innermost inlined location) and to
 the device function that line belongs to. DESIGN.md section 9 quotes its output.
+--outside: the kernel's code before and after that loop instead (the step's head; the env layer,
+the reset and the stores), per basic block: VALU, f64 and branch counts. DESIGN.md section 8,
+round 8, quotes it for the product and the -DF16_ENV_LAYER_REF forms.
 """
 from __future__ import annotations
 
@@ -49,6 +53,53 @@ def frame_loop(body):
     return best
 
 
+def is_f64(line: str) -> bool:
+    t = line.strip().split()
+    return bool(t) and t[0].startswith("v_") and "f64" in t[0]
+
+
+def is_branch(line: str) -> bool:
+    t = line.strip().split()
+    return bool(t) and (t[0].startswith("s_cbranch") or t[0] in ("s_branch", "s_setpc_b64"))
+
+
+def outside(body, a, b, files, cache, min_valu):
+    """The code before and after the frame loop, split at its labels into basic blocks: VALU, f64
+    and branch instructions per block, and the device function most of the block's VALU belongs to."""
+    for title, lo, hi in (("before the frame loop", 0, a), ("after the frame loop", b + 1, len(body))):
+        blocks, cur, loc = [], None, None
+        for l in body[lo:hi]:
+            m = re.match(r"^(\.LBB\w+):", l)
+            if m or cur is None:
+                cur = {"label": m.group(1) if m else "(entry)", "valu": 0, "f64": 0, "br": 0, "exec": 0,
+                       "funcs": collections.Counter()}
+                blocks.append(cur)
+                if m:
+                    continue
+            m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", l)
+            if m:
+                loc = (files.get(int(m.group(1)), "?"), int(m.group(2)))
+                continue
+            if is_valu(l):
+                cur["valu"] += 1
+                cur["f64"] += is_f64(l)
+                cur["funcs"][func_of(cache, *loc) if loc else "?"] += 1
+            cur["br"] += is_branch(l)
+            cur["exec"] += "saveexec" in l
+        tot = {k: sum(x[k] for x in blocks) for k in ("valu", "f64", "br", "exec")}
+        print("  %s: %d blocks, %d VALU (%d f64), %d branches, %d exec-mask saves" % (
+            title, len(blocks), tot["valu"], tot["f64"], tot["br"], tot["exec"]))
+        per_func = collections.Counter()
+        for x in blocks:
+            per_func.update(x["funcs"])
+        print("    VALU by function: " + ", ".join("%s %d" % fc for fc in per_func.most_common(12)))
+        print("    block            VALU  f64   br  mostly")
+        for x in blocks:
+            if x["valu"] >= min_valu:
+                top = x["funcs"].most_common(1)
+                print("    %-14s %6d %4d %4d  %s" % (x["label"], x["valu"], x["f64"], x["br"], top[0][0] if top else ""))
+
+
 def func_of(cache, fname, line):
     path = SOURCES.get(fname)
     if not path:
@@ -88,6 +139,10 @@ def main():
     a, b, n = loop
     print("kernel %s %s\n  frame loop: %d VALU" % (kernel, " ".join(flags), n))
     cache, cur = {}, None
+    if "--outside" in sys.argv:
+        min_valu = int(sys.argv[sys.argv.index("--min-valu") + 1]) if "--min-valu" in sys.argv else 0
+        outside(body, a, b, files, cache, min_valu)
+        return
     per_func, per_line = collections.Counter(), collections.Counter()
     for l in body[a:b]:
         m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", l)
