@@ -53,9 +53,65 @@ def test_library_exports_policy_symbols(L):
     assert L.f16env_abi_version() == abi.F16ENV_ABI_VERSION == 7
 
 
-@pytest.mark.parametrize("k,d,pi_w,vf_w", [(4, 15, [64, 64], [64, 64]), (10, 17, [64, 64], [128, 64])])
+MATRIX_CASES = [pytest.param(*c[:4], id=name) for name, c in policy_ref.MATRIX.items()]
+
+
+def _assert_matrix_instance(k, d, pi_w, vf_w):
+    """A matrix case runs on the kernel instance its row of the matrix states."""
+    for name, c in policy_ref.MATRIX.items():
+        if c[:4] == (k, d, pi_w, vf_w):
+            assert policy_ref.kernel_instance(k, d, pi_w, vf_w) == c[4], name
+
+
+def test_matrix_reaches_the_instances_it_names():
+    """The documented LDS rule (policy_ref.kernel_instance) puts every matrix case on the kernel
+    instance its row states, all four instances occur, and so do the first-layer k-step counts
+    with remainders 0..3 modulo the k loop's batch of four and hidden layers of 1..4 tiles."""
+    for name, (k, d, pi_w, vf_w, inst) in policy_ref.MATRIX.items():
+        assert policy_ref.kernel_instance(k, d, pi_w, vf_w) == inst, name
+        desc = abi.policy_desc(k, d, pi_w, vf_w)
+        assert abi.policy_blob_layout(desc)[1] == policy_ref.blob_floats(k, d, pi_w, vf_w), name
+    cases = policy_ref.MATRIX.values()
+    assert {c[4] for c in cases} == {(15, True), (15, False), (17, True), (17, False)}
+    assert {((c[0] * c[1] + 1) // 2) % 4 for c in cases} == {0, 1, 2, 3}
+    assert {w // 32 for c in cases for w in c[2] + c[3]} == {1, 2, 3, 4}
+    assert {len(c[2]) for c in cases} | {len(c[3]) for c in cases} == {1, 2, 3}
+    # the figures DESIGN section 4 and the matrix quote
+    assert policy_ref.kernel_instance(4, 15, [64, 64], [64, 64]) == (15, True)
+    k, d, pi_w, vf_w, _ = policy_ref.MATRIX["F"]
+    assert policy_ref.blob_floats(k, d, pi_w, vf_w) == 2 * (21888 + 2 * 16512) + 2 * 4128 + 4  # 472 KB
+    assert 4 * 4 * (170 * 33 + 128 * 32) == 155296 <= policy_ref.LDS_BYTES
+
+
+@pytest.mark.parametrize("k,d,pi_w,vf_w", MATRIX_CASES)
+def test_pack_unpack_round_trip(k, d, pi_w, vf_w):
+    """pack_blob, then the documented layout read back (policy_ref.unpack_blob, which shares no
+    code with the packer): every layer, head and log_std bit-equal, every pad position zero, and
+    the pieces account for every float of the blob exactly once."""
+    from f16_jsb_amd.policy import pack_blob
+    _assert_matrix_instance(k, d, pi_w, vf_w)
+    rng = np.random.default_rng(100 * k + d)
+    pi, vf, act, val, log_std = _net(rng, k, d, pi_w, vf_w)
+    blob = pack_blob(abi.policy_desc(k, d, pi_w, vf_w), pi, vf, act, val, log_std).numpy()
+    assert blob.dtype == np.float32 and blob.shape == (policy_ref.blob_floats(k, d, pi_w, vf_w),)
+    u = policy_ref.unpack_blob(k, d, pi_w, vf_w, blob)
+    same = lambda a, b: a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))  # noqa: E731
+    for got, want in ((u["pi"], pi), (u["vf"], vf), ([u["act_head"]], [act]), ([u["val_head"]], [val])):
+        assert len(got) == len(want)
+        for (gw, gb), (w, b) in zip(got, want):
+            assert same(gw, w.numpy()) and same(gb, b.numpy())
+            assert np.all(gw != 0)  # (the random weights are nowhere zero: a zero read back is a miss)
+    assert same(u["log_std"], log_std.numpy())
+    assert np.all(u["claims"] == 1)
+    assert np.all(blob[u["zero"]] == 0) and len(np.unique(u["zero"])) == len(u["zero"])
+    n_weights = sum(w.numel() + b.numel() for w, b in pi + vf + [act, val]) + 4
+    assert n_weights + len(u["zero"]) == blob.size
+
+
+@pytest.mark.parametrize("k,d,pi_w,vf_w", [(4, 15, [64, 64], [64, 64]), (10, 17, [64, 64], [128, 64])] + MATRIX_CASES)
 def test_blob_layout_matches_python_packer(L, k, d, pi_w, vf_w):
     from f16_jsb_amd.policy import pack_blob
+    _assert_matrix_instance(k, d, pi_w, vf_w)
     desc = abi.policy_desc(k, d, pi_w, vf_w)
     off, total = _c_layout(L, desc)
     off_py, total_py = abi.policy_blob_layout(desc)
