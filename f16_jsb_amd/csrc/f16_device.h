@@ -729,30 +729,30 @@ __device__ __forceinline__ float impact_pressure<false>(float mach, float p) {
   }
   return (fabsf(mach) > 0.0f) ? pt - p : 0.0f;
 }
-// calibrated airspeed (kts) from the latched impact pressure
-__device__ __forceinline__ float vcas_from_qc(float qc, const ModelConsts& C) {
-  if (!(qc != 0.0f)) return 0.0f;
-  const float A = qc * C.inv_p_sl + 1.0f;
-  float M = fsqrt(5.0f * (__builtin_amdgcn_exp2f((1.0f / 3.5f) * __builtin_amdgcn_logf(A)) - 1.0f));
-  if (M > 1.0f) {
+// calibrated airspeed (kts) from the latched impact pressure, for f16env_get_state's canonical
+// vc-kts latch (no step reads it). In fp64, as its inverse qc_from_vcas: A = qc / p_sl + 1 rounded
+// to fp32 would lose qc's low bits (half an ulp of A is 3e-5 of vc at 25 kts, 2e-3 at 3 kts), and
+// a vc written by set_state reads back to 1e-6 at every airspeed (tests/test_gpu_state_parity.py).
+__device__ __forceinline__ double vcas_from_qc(float qc, const ModelConsts& C) {
+  if (!(qc != 0.0f)) return 0.0;
+  const double A = (double)qc / (double)C.p_sl + 1.0;
+  double M = sqrt(5.0 * (pow(A, 1.0 / 3.5) - 1.0));
+  if (M > 1.0) {
     // Supersonic: the Rayleigh pitot relation M = c sqrt(A (1 - 1/(7 M^2))^2.5), which the
-    // oracle solves by 10 fixed-point steps (contraction ~0.3 per step, converged to fp32
-    // precision), solved here by Newton on y = M^2 from the subsonic estimate: 3 steps, each
-    // quadratically convergent (9 transcendentals instead of 30).
-    float y = M * M;
-    const float cA = 0.8812848543473311f * 0.8812848543473311f * A;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const float iy = rcpf(y);
-      const float t = 1.0f - (1.0f / 7.0f) * iy;
-      const float tst = t * fsqrt(t);
-      const float g = cA * t * tst;                               // cA t^2.5
-      const float dg = (2.5f / 7.0f) * cA * tst * iy * iy;        // dg/dy
-      y -= (y - g) * rcpf(1.0f - dg);
+    // oracle solves by 10 fixed-point steps, solved here by Newton on y = M^2 from the subsonic
+    // estimate: 6 steps, each quadratically convergent.
+    double y = M * M;
+    const double cA = 0.8812848543473311 * 0.8812848543473311 * A;
+    for (int i = 0; i < 6; ++i) {
+      const double t = 1.0 - 1.0 / (7.0 * y);
+      const double tst = t * sqrt(t);
+      const double g = cA * t * tst;                          // cA t^2.5
+      const double dg = (2.5 / 7.0) * cA * tst / (y * y);     // dg/dy
+      y -= (y - g) / (1.0 - dg);
     }
-    M = fsqrt(y);
+    M = sqrt(y);
   }
-  return C.a_sl * M * C.kts_per_fps;
+  return (double)C.a_sl * M * (double)C.kts_per_fps;
 }
 
 // inverse of vcas_from_qc (fp64): the impact pressure of a calibrated airspeed, for
