@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .abi import F16ENV_ABI_VERSION, EnvConfig, PolicyDesc, RolloutSlot
+from .abi import F16ENV_ABI_VERSION, EnvConfig, PolicyDesc, RolloutSlot, RolloutView
 
 LIB_PATH = os.environ.get("F16ENV_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libf16env.so")
 
@@ -90,6 +90,9 @@ def lib():
     L.f16env_sample_actions.argtypes = [vp, vp, u64, u64, vp]
     L.f16env_gae.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, vp, ctypes.c_double,
                              ctypes.c_double, vp, vp]
+    # bound only when present: an older library named through F16ENV_LIB still loads, and the
+    # sampler (rollout.rollout_minibatch) then raises F16EnvError
+    _set(L, "f16env_rollout_minibatch", [vp, ctypes.POINTER(RolloutView), i64, vp] + [vp] * 6, i32)
     L.f16env_features.argtypes = [vp, ctypes.c_int64, vp, vp]
     _set(L, "f16env_poses", [vp, ctypes.c_int64, vp, ctypes.c_int64, vp], i32)
     L.f16env_step_kernel_name.argtypes = [vp]
@@ -138,5 +141,5 @@ EXPORTED_SYMBOLS = (
     "f16env_get_state",
     "f16env_set_state", "f16env_trim", "f16env_sample_actions", "f16env_gae", "f16env_features", "f16env_poses", "f16env_step_kernel_name", "f16env_step_waves_per_simd", "f16env_step_variant", "f16env_profile_begin", "f16env_profile_end", "f16env_profile_times",
     "f16env_algorithmic_bytes_per_env_step", "f16env_last_error",
-    "f16env_policy_blob_layout", "f16env_policy_forward",
+    "f16env_policy_blob_layout", "f16env_policy_forward", "f16env_rollout_minibatch",
 )

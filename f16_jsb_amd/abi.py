@@ -164,6 +164,25 @@ class RolloutSlot(ctypes.Structure):
     ]
 
 
+class RolloutView(ctypes.Structure):
+    """F16RolloutView (include/f16env.h): the finished rollout f16env_rollout_minibatch samples,
+    one device's buffer (world 1) or the rank-major gather of `world` shards."""
+    _fields_ = [
+        ("world", ctypes.c_int32),
+        ("K", ctypes.c_int32),
+        ("n_steps", ctypes.c_int64),
+        ("n_envs", ctypes.c_int64),
+        ("frames", ctypes.c_void_p),
+        ("obs0", ctypes.c_void_p),
+        ("episode_starts", ctypes.c_void_p),
+        ("values", ctypes.c_void_p),
+        ("log_probs", ctypes.c_void_p),
+        ("advantages", ctypes.c_void_p),
+        ("returns", ctypes.c_void_p),
+        ("actions", ctypes.c_void_p),
+    ]
+
+
 # ABI 7: the device policy (f16env_policy_forward)
 F16_POLICY_ACT_TANH = 0
 F16_POLICY_ACT_RELU = 1

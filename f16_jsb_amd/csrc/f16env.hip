@@ -3476,6 +3476,169 @@ int f16env_gae(void* stream, int64_t n_steps, int64_t n_envs, const float* rewar
   return 0;
 }
 
+// One minibatch of the PPO update (include/f16env.h f16env_rollout_minibatch; buffers.py:481-521):
+// a 256-thread block takes MB_SAMPLES samples.
+// Phase 1, one lane per sample in each of the four waves (every wave decodes the index itself; what
+// it then moves is wave-uniform): wave 0 reads the sample's at most K-1 episode starts and writes
+// the source of each of its K output frames into the LDS table, waves 1-3 move the float4 action
+// and the four scalars.
+// Phase 2: the block's 64 K 15 contiguous output floats as float4 stores, each dword loaded
+// through the table (a source frame is a 60-B run at 4-B alignment).
+// Table entry: >= 0 an element offset into frames, -1 - (element offset into obs0) for a source
+// step before step 0, MB_INVALID for a row with nothing to read (index out of range, or a sample
+// past the batch): such a row is never turned into an address and reads as quiet NaN.
+// THE GUARD: `ok` below is the only place an index becomes coordinates, and it holds only for
+// 0 <= i < W N T, hence r < W, n < N, t < T; source steps lie in [t-K+1, t], those >= 0 index
+// frames below T, those < 0 index obs0 at step + K-1 in [0, K-2]; starts are read at steps
+// t-d >= 0 only. Every store is bounded by the batch (b < batch; e + i < limit).
+constexpr int MB_SAMPLES = 64;
+constexpr int64_t MB_INVALID = INT64_MIN;
+constexpr uint32_t MB_QNAN = 0x7FC00000u;
+
+struct MbArgs {
+  F16RolloutView v;
+  int64_t batch, total;  // total = W N T
+  const int64_t* idx;
+  uint32_t* obs;
+  uint4* act;
+  uint32_t *val, *lp, *adv, *ret;
+};
+
+__global__ __launch_bounds__(256) void f16_minibatch_kernel(MbArgs a) {
+  extern __shared__ int64_t mb_src[];  // [MB_SAMPLES * K]
+  const int K = a.v.K;
+  const int64_t T = a.v.n_steps, N = a.v.n_envs;
+  const int tid = threadIdx.x, s = tid & 63, role = tid >> 6;
+  const int64_t b = (int64_t)blockIdx.x * MB_SAMPLES + s;
+  bool ok = false;
+  int64_t t = 0, r = 0, n = 0;
+  if (b < a.batch) {
+    const int64_t i = a.idx[b];
+    ok = (uint64_t)i < (uint64_t)a.total;
+    if (ok) {
+      if (a.total <= 0xFFFFFFFFll) {  // (uniform) 32-bit divides where the whole rollout allows
+        const uint32_t g = (uint32_t)i / (uint32_t)T, rr = g / (uint32_t)N;
+        t = (uint32_t)i - g * (uint32_t)T, r = rr, n = g - rr * (uint32_t)N;
+      } else {
+        const int64_t g = i / T;
+        t = i - g * T, r = g / N, n = g - r * N;
+      }
+    }
+  }
+  const int64_t cell = (r * T + t) * N + n;  // the transition's place in a (W, T, N) array
+  if (role == 0) {
+    int64_t* row = mb_src + s * K;
+    if (!ok) {
+      for (int j = 0; j < K; ++j) row[j] = MB_INVALID;
+    } else {
+      int64_t last = t - K;  // below every source step: no bound
+      const uint32_t* es = reinterpret_cast<const uint32_t*>(a.v.episode_starts) + cell;
+      const int look = (int)(t + 1 < (int64_t)(K - 1) ? t + 1 : (int64_t)(K - 1));
+#pragma unroll 4
+      for (int d = 0; d < look; ++d) {
+        // non-zero as torch's .bool(): +-0 is no start, anything else (NaN too) is
+        const bool start = (es[-(int64_t)d * N] & 0x7FFFFFFFu) != 0u;
+        const int64_t u = start ? t - d : last;
+        last = u > last ? u : last;
+      }
+      const int64_t f0 = (r * T * N + n) * F16_OBS_DIM, fs = N * F16_OBS_DIM;
+      const int64_t z0 = (r * N + n) * K * F16_OBS_DIM;
+      for (int j = 0; j < K; ++j) {
+        const int64_t want = t - (K - 1) + j, step = want > last ? want : last;
+        row[j] = step >= 0 ? f0 + step * fs : -1 - (z0 + (step + K - 1) * F16_OBS_DIM);
+      }
+    }
+  } else if (b < a.batch) {
+    if (role == 1) {
+      uint4 q = {MB_QNAN, MB_QNAN, MB_QNAN, MB_QNAN};
+      if (ok) q = reinterpret_cast<const uint4*>(a.v.actions)[cell];
+      a.act[b] = q;
+    } else {
+      const uint32_t* x = reinterpret_cast<const uint32_t*>(role == 2 ? a.v.values : a.v.advantages);
+      const uint32_t* y = reinterpret_cast<const uint32_t*>(role == 2 ? a.v.log_probs : a.v.returns);
+      uint32_t xv = MB_QNAN, yv = MB_QNAN;
+      if (ok) xv = x[cell], yv = y[cell];
+      (role == 2 ? a.val : a.adv)[b] = xv;
+      (role == 2 ? a.lp : a.ret)[b] = yv;
+    }
+  }
+  __syncthreads();
+  const int rows = MB_SAMPLES * K;
+  const int64_t blk = (int64_t)blockIdx.x * rows * F16_OBS_DIM;  // floats; a multiple of 4
+  const int64_t left = a.batch * K * F16_OBS_DIM - blk;          // floats of the output from blk on
+  const int limit = (int)(left < (int64_t)rows * F16_OBS_DIM ? left : (int64_t)rows * F16_OBS_DIM);
+  const uint32_t* frames = reinterpret_cast<const uint32_t*>(a.v.frames);
+  const uint32_t* obs0 = reinterpret_cast<const uint32_t*>(a.v.obs0);
+  uint32_t* out = a.obs + blk;
+  for (int e = 4 * tid; e < limit; e += 4 * 256) {
+    const int fr = e / F16_OBS_DIM, c = e - fr * F16_OBS_DIM;
+    const int64_t o0 = mb_src[fr], o1 = mb_src[fr + 1 < rows ? fr + 1 : rows - 1];
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool wrap = c + i >= F16_OBS_DIM;
+      const int64_t off = wrap ? o1 : o0;
+      const int cc = wrap ? c + i - F16_OBS_DIM : c + i;
+      w[i] = MB_QNAN;
+      if (off != MB_INVALID && e + i < limit) w[i] = (off >= 0 ? frames + off : obs0 + (-1 - off))[cc];
+    }
+    if (e + 3 < limit) {
+      *reinterpret_cast<uint4*>(out + e) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+      for (int i = 0; e + i < limit; ++i) out[e + i] = w[i];
+    }
+  }
+}
+
+int f16env_rollout_minibatch(void* stream, const F16RolloutView* view, int64_t batch, const int64_t* indices,
+                             float* obs, float* actions, float* old_values, float* old_log_probs,
+                             float* advantages, float* returns) {
+  if (!view) return set_err(-1, "null rollout view");
+  if (batch < 0) return set_err(-1, "batch must be >= 0");
+  if (view->K < 1 || view->K > 64) return set_err(-1, "view K must be in [1, 64]");
+  if (view->world < 1 || view->n_steps < 1 || view->n_envs < 1)
+    return set_err(-1, "view world, n_steps and n_envs must be >= 1");
+  // the largest element offset (W T N 15, and W N K 15 for obs0) stays far inside int64
+  if ((double)view->world * (double)view->n_steps * (double)view->n_envs * (F16_OBS_DIM * 64.0) >= 4.0e18)
+    return set_err(-1, "view world x n_steps x n_envs too large");
+  if (batch == 0) return 0;
+  if (!view->frames) return set_err(-1, "view frames is NULL");
+  if (!view->obs0) return set_err(-1, "view obs0 is NULL");
+  if (!view->episode_starts) return set_err(-1, "view episode_starts is NULL");
+  if (!view->values) return set_err(-1, "view values is NULL");
+  if (!view->log_probs) return set_err(-1, "view log_probs is NULL");
+  if (!view->advantages) return set_err(-1, "view advantages is NULL");
+  if (!view->returns) return set_err(-1, "view returns is NULL");
+  if (!view->actions) return set_err(-1, "view actions is NULL");
+  if (!indices || !obs || !actions || !old_values || !old_log_probs || !advantages || !returns)
+    return set_err(-1, "null argument (indices and the six outputs are required)");
+  if ((((uintptr_t)view->actions) | ((uintptr_t)obs) | ((uintptr_t)actions)) & 15)
+    return set_err(-1, "view actions and the obs / actions outputs must be 16-byte aligned");
+  if ((((uintptr_t)view->frames) | ((uintptr_t)view->obs0) | ((uintptr_t)view->episode_starts) |
+       ((uintptr_t)view->values) | ((uintptr_t)view->log_probs) | ((uintptr_t)view->advantages) |
+       ((uintptr_t)view->returns) | ((uintptr_t)old_values) | ((uintptr_t)old_log_probs) | ((uintptr_t)advantages) |
+       ((uintptr_t)returns)) & 3)
+    return set_err(-1, "float arrays must be float-aligned");
+  if (((uintptr_t)indices & 7) != 0) return set_err(-1, "indices must be 8-byte aligned");
+  const int64_t blocks = (batch + MB_SAMPLES - 1) / MB_SAMPLES;
+  if (blocks > 0x7fffffffLL) return set_err(-1, "batch too large");
+  MbArgs a;
+  a.v = *view;
+  a.batch = batch;
+  a.total = (int64_t)view->world * view->n_steps * view->n_envs;
+  a.idx = indices;
+  a.obs = reinterpret_cast<uint32_t*>(obs);
+  a.act = reinterpret_cast<uint4*>(actions);
+  a.val = reinterpret_cast<uint32_t*>(old_values);
+  a.lp = reinterpret_cast<uint32_t*>(old_log_probs);
+  a.adv = reinterpret_cast<uint32_t*>(advantages);
+  a.ret = reinterpret_cast<uint32_t*>(returns);
+  hipLaunchKernelGGL(f16_minibatch_kernel, dim3((unsigned)blocks), dim3(256),
+                     (size_t)MB_SAMPLES * view->K * sizeof(int64_t), (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int f16env_policy_blob_layout(const f16_policy_desc* desc, int64_t* offsets_out, int64_t* n_floats_out) {
   if (const char* m = policy_desc_error(desc)) return set_err(-1, m);
   if (!offsets_out || !n_floats_out) return set_err(-1, "null argument");

@@ -11,15 +11,20 @@ Frame dedup: a stacked observation is K overlapping frames, so th
 only the newest frame per step plus the stack before step 0, and rebuilds any step's stack
 from those and `episode_starts` (a reset observation is K copies of its first frame). That
 cuts the gathered observation bytes by K.
+
+The update's data side (buffers.py:481-521): `DeviceRolloutBuffer.get` / `minibatches` yield
+shuffled minibatches, each gathered from the deduplicated log by one `f16env_rollout_minibatch`
+launch, so the stacked (T, N, K, 15) array is never materialised.
 """
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from typing import Dict, Optional
 
 import torch
 
-from .abi import F16_FLAG_NO_AUTORESET, F16_OBS_DIM, F16_SLOT_CLIP, RolloutSlot
+from .abi import F16_FLAG_NO_AUTORESET, F16_OBS_DIM, F16_SLOT_CLIP, RolloutSlot, RolloutView
 
 FIELDS = ("frames", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns")
 # device memory the deferred timeout bootstrap may take for its stash of terminal observations
@@ -90,6 +95,21 @@ class DeviceRolloutBuffer:
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         return {f: getattr(self, f) for f in FIELDS} | {"obs0": self.obs0}
+
+    def get(self, batch_size: Optional[int] = None, indices=None, generator=None):
+        """RolloutBuffer.get (buffers.py:481-506) on the device: a generator of RolloutSamples over
+        one shuffled pass of the n_steps * n_envs transitions, each minibatch gathered by one
+        f16env_rollout_minibatch launch from the frame-deduplicated log (nothing proportional to
+        T * N * K is ever allocated; see rollout_minibatch and flat_index for the order).
+        The permutation is `indices` when given (a numpy array or CPU tensor, e.g. SB3's own
+        np.random.permutation(T * N), is moved to the device once; range-checked once), else
+        torch.randperm(T * N, device=..., generator=generator) (whose own sort needs a few times the
+        permutation's 8 B per transition while it runs; the pass itself holds the permutation and
+        the minibatches in flight). batch_size None: one batch of everything; a short last
+        minibatch is yielded as it is; every yield is fresh tensors."""
+        if not self.full:
+            raise RuntimeError("rollout buffer is not full (pos %d of %d)" % (self.pos, self.n_steps))
+        return _minibatches(self, self.k, self.n_steps * self.n_envs, self.device, batch_size, indices, generator)
 
 
 ACTION_LOW = (-1.0, -1.0, -1.0, 0.0)   # jsbsim_gym.py:143-148 action Box
@@ -365,3 +385,139 @@ def env_major(x: torch.Tensor) -> torch.Tensor:
     """(world, T, N, ...) rank-major gather output -> (T, world * N, ...) (a copy)."""
     w, T, N = x.shape[:3]
     return x.transpose(0, 1).reshape((T, w * N) + tuple(x.shape[3:]))
+
+
+# ------------------------------------------------------------------------------------------------
+# The PPO update's data side: shuffled minibatches straight from the frame-deduplicated log.
+RolloutSamples = namedtuple("RolloutSamples", ("observations", "actions", "old_values", "old_log_prob",
+                                               "advantages", "returns"))
+RolloutSamples.__doc__ = """One minibatch of device tensors, SB3's RolloutBufferSamples field for field
+(type_aliases.py): observations (B, K, 15), actions (B, 4), old_values, old_log_prob, advantages,
+returns (B,)."""
+
+VIEW_FIELDS = ("frames", "obs0", "episode_starts", "values", "log_probs", "advantages", "returns", "actions")
+
+
+def flat_index(t, env, n_steps: int):
+    """Flat index of transition (step t, global env) in SB3's swap_and_flatten order over the
+    (T, n_envs) buffer (buffers.py:36-50, :493-503): env * n_steps + t. After gather_to_rank0 the
+    global env of shard r's env n is r * n_envs + n. Ints, numpy arrays or tensors."""
+    return env * n_steps + t
+
+
+def unflatten_index(i, n_steps: int):
+    """flat_index's inverse: (t, env)."""
+    return i % n_steps, i // n_steps
+
+
+class _View:
+    """The checked source of a sampler: the ctypes view, what keeps its tensors alive, its sizes."""
+
+    def __init__(self, src, k=None):
+        sd = src.state_dict() if hasattr(src, "state_dict") else src
+        missing = [f for f in VIEW_FIELDS if f not in sd]
+        if missing:
+            raise ValueError("rollout source lacks %s" % ", ".join(missing))
+        fr = sd["frames"]
+        if not isinstance(fr, torch.Tensor) or fr.dim() not in (3, 4):
+            raise ValueError("frames must be a (T, N, 15) or (world, T, N, 15) tensor")
+        lead = tuple(fr.shape[:-1])
+        W, T, N = ((1,) + lead) if fr.dim() == 3 else lead
+        wrap = (lambda *s: s) if fr.dim() == 3 else (lambda *s: (W,) + s)
+        if k is None:
+            k = getattr(src, "k", None) or sd["obs0"].shape[-2]
+        k = int(k)
+        if not 1 <= k <= 64 or min(W, T, N) < 1:
+            raise ValueError("stack_k must be in 1..64 and world, n_steps, n_envs >= 1")
+        shapes = {"frames": wrap(T, N, F16_OBS_DIM), "obs0": wrap(N, k, F16_OBS_DIM), "actions": wrap(T, N, 4)}
+        if fr.device.type != "cuda":
+            raise ValueError("the minibatch sampler runs on the GPU (f16env_rollout_minibatch); the rollout is on %s"
+                             % fr.device)
+        for f in VIEW_FIELDS:
+            x = sd[f]
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != fr.device \
+                    or not x.is_contiguous() or tuple(x.shape) != shapes.get(f, wrap(T, N)) \
+                    or x.data_ptr() % (16 if f == "actions" else 4):
+                raise ValueError("%s must be a contiguous float32 %s tensor on %s%s"
+                                 % (f, shapes.get(f, wrap(T, N)), fr.device, ", 16-byte aligned" if f == "actions" else ""))
+        self.device, self.k, self.total = fr.device, k, W * T * N
+        self.tensors = tuple(sd[f] for f in VIEW_FIELDS)
+        self.view = RolloutView(W, k, T, N, *(x.data_ptr() for x in self.tensors))
+        self.ref = ctypes.byref(self.view)
+
+
+def _check_samples(out, batch: int, k: int, device):
+    shapes = ((batch, k, F16_OBS_DIM), (batch, 4), (batch,), (batch,), (batch,), (batch,))
+    if not isinstance(out, tuple) or len(out) != 6:
+        raise ValueError("out must be a RolloutSamples of six tensors")
+    for x, shape, name in zip(out, shapes, RolloutSamples._fields):
+        align = 16 if len(shape) > 1 else 4
+        if not isinstance(x, torch.Tensor) or x.device != device or x.dtype != torch.float32 \
+                or not x.is_contiguous() or tuple(x.shape) != shape or x.data_ptr() % align:
+            raise ValueError("out.%s must be a contiguous %d-byte aligned float32 %s tensor on %s"
+                             % (name, align, shape, device))
+
+
+def rollout_minibatch(src, indices, k: Optional[int] = None, out: Optional[RolloutSamples] = None) -> RolloutSamples:
+    """RolloutBuffer._get_samples (buffers.py:508-521) for one batch of flat indices, one launch of
+    f16env_rollout_minibatch on the current stream.
+    src: a full DeviceRolloutBuffer, its state_dict(), or the dict gather_to_rank0 returns (world
+    from frames.dim(); the rank-major tensors are used in place, no env_major copy); k the stack
+    depth (default: the buffer's, or obs0's). indices: int64 tensor on the device, flat_index order.
+    Row b of every output is transition indices[b]; observations are rebuilt per sample by
+    rebuild_observations' rule. An index outside [0, world * n_envs * n_steps) reads nothing and
+    yields a row of NaN (DeviceRolloutBuffer.get range-checks its caller's indices instead).
+    out: caller-owned RolloutSamples to write into. With `out` given the call allocates nothing and
+    never synchronises, so it can be captured in a HIP graph."""
+    from ._lib import F16EnvError, check, lib
+
+    v = src if isinstance(src, _View) else _View(src, k)
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64 or indices.device != v.device \
+            or indices.dim() != 1 or not indices.is_contiguous():
+        raise ValueError("indices must be a contiguous 1-D int64 tensor on %s" % v.device)
+    batch = indices.numel()
+    if out is None:
+        e = lambda *s: torch.empty(s, dtype=torch.float32, device=v.device)  # noqa: E731
+        out = RolloutSamples(e(batch, v.k, F16_OBS_DIM), e(batch, 4), e(batch), e(batch), e(batch), e(batch))
+    else:
+        _check_samples(out, batch, v.k, v.device)
+    fn = getattr(lib(), "f16env_rollout_minibatch", None)
+    if fn is None:
+        raise F16EnvError("this libf16env.so has no f16env_rollout_minibatch: rebuild it (python -m f16_jsb_amd.build)")
+    if batch:
+        check(fn(ctypes.c_void_p(torch.cuda.current_stream(v.device).cuda_stream), v.ref, batch, indices.data_ptr(),
+                 *(x.data_ptr() for x in out)), "f16env_rollout_minibatch")
+    return out
+
+
+def _minibatches(src, k, total: int, device, batch_size, indices, generator):
+    """The checks of a sampling pass, made when it is asked for; then its generator."""
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    if indices is not None:
+        perm = torch.as_tensor(indices)
+        if perm.dim() != 1 or perm.dtype not in (torch.int64, torch.int32):
+            raise ValueError("indices must be a 1-D integer array")
+        if perm.numel():
+            lo, hi = (int(x) for x in torch.aminmax(perm))
+            if lo < 0 or hi >= total:
+                raise ValueError("indices must lie in [0, %d), got [%d, %d]" % (total, lo, hi))
+    view = _View(src, k)
+    if indices is None:
+        perm = torch.randperm(total, device=device, generator=generator)
+    else:
+        perm = perm.to(device=device, dtype=torch.int64).contiguous()
+    step = perm.numel() if batch_size is None else int(batch_size)
+
+    def gen():
+        for i in range(0, perm.numel(), max(1, step)):
+            yield rollout_minibatch(view, perm[i:i + step])
+    return gen()
+
+
+def minibatches(gathered: Dict[str, torch.Tensor], k: Optional[int] = None, batch_size: Optional[int] = None,
+                indices=None, generator=None):
+    """DeviceRolloutBuffer.get over the dict gather_to_rank0 returns on rank 0: one shuffled pass
+    over all world * n_envs * n_steps transitions, the rank-major tensors read in place."""
+    fr = gathered["frames"]
+    return _minibatches(gathered, k, int(fr.numel() // F16_OBS_DIM), fr.device, batch_size, indices, generator)

@@ -30,6 +30,8 @@
  *   f16env_bootstrap_stash / f16env_bootstrap_apply <- the same, deferred to the end of the
  *                      rollout (one value evaluation over the stashed terminal observations)
  *   f16env_gae      <- stable_baselines3/common/buffers.py:403-438 (device rollout, 8f rank 1)
+ *   f16env_rollout_minibatch <- buffers.py:481-521 RolloutBuffer.get / _get_samples (one minibatch
+ *                      of the shuffled rollout, stacks rebuilt from the frame-deduplicated log)
  *   f16env_policy_forward <- on_policy_algorithm.py:199-202 policy(obs_tensor): common/policies.py
  *                      ActorCriticPolicy.forward with torch_layers.py MlpExtractor's separate pi / vf
  *                      MLPs and a DiagGaussianDistribution, one launch
@@ -59,7 +61,10 @@ extern "C" {
  * 6 (round 6): new f16env_sample_actions_steps and f16env_window_resets_deferred; nothing else
  * changed.
  * 7: new f16_policy_desc, f16env_policy_blob_layout and f16env_policy_forward (the actor-critic
- * MLP forward of a rollout as one kernel); nothing else changed. */
+ * MLP forward of a rollout as one kernel); nothing else changed.
+ * Still 7: new F16RolloutView and f16env_rollout_minibatch (the PPO update's minibatch sampler).
+ * A symbol was added and no signature changed, so a caller built against the earlier 7 runs
+ * unchanged; a binding that wants the sampler looks the symbol up and reports its absence. */
 #define F16ENV_ABI_VERSION 7
 
 /* Frame layout (jsbsim_gym.py:12-25 STATE_FORMAT + goal, :172-197) */
@@ -465,6 +470,41 @@ int f16env_sample_actions_steps(f16env_t h, void* stream, uint64_t seed, uint64_
 int f16env_gae(void* stream, int64_t n_steps, int64_t n_envs, const float* rewards, const float* values,
                const float* episode_starts, const float* last_values, const uint8_t* dones, double gamma,
                double gae_lambda, float* advantages, float* returns);
+
+/* One minibatch of a finished device rollout (stable_baselines3/common/buffers.py:481-521,
+ * RolloutBuffer.get and _get_samples), gathered by ONE launch straight from the frame-deduplicated
+ * log: no stacked (T, N, K, 15) observation array ever exists. The view names the rollout:
+ *   world W, n_steps T, n_envs N (per shard), K
+ *   frames (W, T, N, 15), obs0 (W, N, K, 15), actions (W, T, N, 4; 16-B aligned) and
+ *   episode_starts, values, log_probs, advantages, returns (W, T, N): contiguous float32 on the
+ *   device. W = 1 is one device's buffer; W > 1 the rank-major gather of W shards, used in place.
+ * indices: `batch` int64 on the device. Flat index i names the transition in SB3's
+ * swap_and_flatten order over the (T, W*N) env-major buffer (buffers.py:36-50, :493-503):
+ *   g = i / T (global env), t = i % T (step), r = g / N (shard), n = g % N (env of the shard).
+ * Outputs, row b from indices[b]:
+ *   obs (batch, K, 15; 16-B aligned): obs[j] = frame[max(t - (K-1) + j, s_t)], s_t the last step
+ *     <= t whose episode_starts is non-zero (none: no bound); a source step below 0 is
+ *     obs0[r][n][step + K - 1]. Only the starts in (t - K + 1, t] are read.
+ *   actions (batch, 4; 16-B aligned), old_values, old_log_probs, advantages, returns (batch).
+ * Every value is moved as 32 bits: NaN payloads, infinities and -0 survive. An index outside
+ * [0, W*N*T) is never turned into an address: that row of all six outputs is quiet NaN
+ * (0x7FC00000). batch == 0: returns 0, launches nothing. A bad argument returns < 0 before any
+ * launch. No handle; stream-ordered; no sync and no allocation (safe under stream capture). */
+typedef struct F16RolloutView {
+  int32_t world, K;
+  int64_t n_steps, n_envs;
+  const float* frames;
+  const float* obs0;
+  const float* episode_starts;
+  const float* values;
+  const float* log_probs;
+  const float* advantages;
+  const float* returns;
+  const float* actions;
+} F16RolloutView;
+int f16env_rollout_minibatch(void* stream, const F16RolloutView* view, int64_t batch, const int64_t* indices,
+                             float* obs, float* actions, float* old_values, float* old_log_probs,
+                             float* advantages, float* returns);
 
 /* ABI 7. The policy of a rollout on the device: actions, values, log_probs = policy(obs) for
  * stable_baselines3's ActorCriticPolicy with separate pi / vf MLPs (policies.py
