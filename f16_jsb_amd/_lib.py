@@ -93,6 +93,10 @@ def lib():
     # bound only when present: an older library named through F16ENV_LIB still loads, and the
     # sampler (rollout.rollout_minibatch) then raises F16EnvError
     _set(L, "f16env_rollout_minibatch", [vp, ctypes.POINTER(RolloutView), i64, vp] + [vp] * 6, i32)
+    # (the same for the policy's backward: DevicePolicy's gradient calls raise F16EnvError without it)
+    _set(L, "f16env_policy_backward_workspace", [ctypes.POINTER(PolicyDesc), i64, i32, ctypes.POINTER(i64)], i32)
+    _set(L, "f16env_policy_backward", [vp, ctypes.POINTER(PolicyDesc), vp, i64, vp, i64, i64, vp, vp, vp, i64, i32, vp],
+         i32)
     L.f16env_features.argtypes = [vp, ctypes.c_int64, vp, vp]
     _set(L, "f16env_poses", [vp, ctypes.c_int64, vp, ctypes.c_int64, vp], i32)
     L.f16env_step_kernel_name.argtypes = [vp]
@@ -142,4 +146,5 @@ EXPORTED_SYMBOLS = (
     "f16env_set_state", "f16env_trim", "f16env_sample_actions", "f16env_gae", "f16env_features", "f16env_poses", "f16env_step_kernel_name", "f16env_step_waves_per_simd", "f16env_step_variant", "f16env_profile_begin", "f16env_profile_end", "f16env_profile_times",
     "f16env_algorithmic_bytes_per_env_step", "f16env_last_error",
     "f16env_policy_blob_layout", "f16env_policy_forward", "f16env_rollout_minibatch",
+    "f16env_policy_backward_workspace", "f16env_policy_backward",
 )

@@ -1,5 +1,6 @@
 // f16_policy.h -- the actor-critic MLP forward of a rollout as one HIP kernel (gfx950), and the
-// host side of f16env_policy_blob_layout / f16env_policy_forward (include/f16env.h, ABI 7).
+// host side of f16env_policy_blob_layout / f16env_policy_forward (include/f16env.h, ABI 7); below
+// it the backward of the two MLPs in the blob's layout (f16env_policy_backward).
 // Included by f16env.hip after its error handling and Philox (set_err, HIPCHK, philox).
 //
 // actions, values, log_probs = policy(obs) for stable_baselines3's ActorCriticPolicy with separate
@@ -272,6 +273,256 @@ __global__ __launch_bounds__(64 * POL_WAVES) void f16_policy_forward_kernel(cons
 }
 
 // ------------------------------------------------------------------------------------------
+// The backward (f16env_policy_backward): grad_blob = sum over rows of d_mean . d mean / d blob +
+// d_values d value / d blob, in the blob's own layout. A wave owns 32 rows at a time, as in the
+// forward, and keeps per tile in its own LDS: the observation image, ONE branch's recomputed
+// activations (an image per layer) and a delta image [unit][row], all at the row stride POL_XS
+// (33: a lane walks them across units as well as across rows). Per layer, from the head down:
+//   dW^T = X^T Delta   MFMA rows = 32 inputs, columns = 32 units, k = the tile's 32 rows
+//     A: lane l holds X[row 2 s + (l >> 5)] of input 32 ti + (l & 31)   (input image, across inputs)
+//     B: lane l holds Delta[row 2 s + (l >> 5)] of unit 32 to + (l & 31) (delta image, across units)
+//     C: register r = input 32 ti + pol_unit(r, l >> 5), unit 32 to + (l & 31): blob element
+//        w_off + ((to 2 nks + input) 32 + unit), so a register of 32 lanes is one 128-B line
+//   Delta_prev^T = W^T Delta^T   MFMA rows = 32 inputs, k = units, columns = the 32 rows
+//     A: lane l holds W[unit 32 to + 16 (l >> 5) + s][input 32 ti + (l & 31)], s = 0..15: sixteen
+//        consecutive floats of the packed layer (k runs over the units in that order; B agrees)
+//     B: lane l holds Delta[unit 32 to + 16 (l >> 5) + s][row l & 31]
+//     C: as the forward's; times the activation's derivative on the stored h, into the delta image
+//   db = the delta image summed along its rows.
+// The wave accumulates into its own slice of the workspace (slot = block * waves + wave; tiles
+// slot, slot + slots, ...), first tile stored, later tiles added in tile order; a second kernel
+// sums the slices that got a tile in slot order. No atomics: the bits depend on (desc, n,
+// max_blocks) alone.
+constexpr int POL_BWD_BLOCKS = 256;  // default grid limit: the MI355X's CU count
+
+struct PolicyBwdArgs {
+  const float* blob;
+  const float* obs;
+  const float* d_mean;
+  const float* d_values;
+  float* ws;
+  int64_t n, row_stride, frame_stride, ntiles, nslots;
+  int32_t K, in_dim, obs_floats, act_floats, wave_floats, blob_floats, n_pi, n_vf, relu, waves;
+  PolicyOp ops[POL_OPS];
+};
+
+// one hidden layer of the recompute: the forward's chain and activation, into the layer's own image
+template <int TOUT>
+__device__ __forceinline__ void policy_bwd_hidden(const float* __restrict__ wb, const PolicyOp op, const float* xin,
+                                                  float* hout, const int relu, const int lane, pol_f32x16 (&acc)[4]) {
+  policy_gemm<TOUT>(wb, op, xin, POL_XS, lane, acc);
+  const int j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int to = 0; to < TOUT; ++to) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float v = acc[to][r];
+      hout[(32 * to + pol_unit(r, h)) * POL_XS + j] = relu ? (v < 0.0f ? 0.0f : v) : policy_tanh(v);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// the slice's weight piece (+)= X^T Delta over the tile's rows (inputs past the piece are not stored)
+template <int TOUT>
+__device__ __forceinline__ void policy_bwd_dw(float* g, const PolicyOp op, const float* xin, const float* dl,
+                                              const bool first, const int lane) {
+  const int j = lane & 31, h = lane >> 5;
+  const int nin = 2 * op.nks;
+  float* gp = g + op.w_off + j;
+  const float* dp = dl + j * POL_XS + h;
+  for (int i0 = 0; i0 < nin; i0 += 32) {
+    pol_f32x16 acc[TOUT];
+#pragma unroll
+    for (int to = 0; to < TOUT; ++to) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = i0 + pol_unit(r, h);
+        acc[to][r] = (first || i >= nin) ? 0.0f : gp[(to * nin + i) * 32];
+      }
+    }
+    const int ia = i0 + j < nin ? i0 + j : nin - 1;  // (rows of the MFMA past the piece repeat its last input)
+    const float* xp = xin + ia * POL_XS + h;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const float x = xp[2 * s];
+#pragma unroll
+      for (int to = 0; to < TOUT; ++to)
+        acc[to] = __builtin_amdgcn_mfma_f32_32x32x2f32(x, dp[to * 32 * POL_XS + 2 * s], acc[to], 0, 0, 0);
+    }
+#pragma unroll
+    for (int to = 0; to < TOUT; ++to) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = i0 + pol_unit(r, h);
+        if (i < nin) gp[(to * nin + i) * 32] = acc[to][r];
+      }
+    }
+  }
+}
+
+// the slice's bias piece (+)= the delta image summed over the tile's rows, in row order
+__device__ __forceinline__ void policy_bwd_db(float* g, const PolicyOp op, const float* dl, const bool first,
+                                              const int lane) {
+  for (int u = lane; u < 32 * op.tout; u += 64) {
+    float s = 0.0f;
+#pragma unroll
+    for (int r = 0; r < POL_ROWS; ++r) s += dl[u * POL_XS + r];
+    float* p = g + op.b_off + u;
+    *p = first ? s : *p + s;
+  }
+}
+
+// the delta image <- (W^T Delta) act'(h) for the layer below `op` (TIN tiles wide, image hprev);
+// rows past n - 1 (valid == false for the lane's row) are forced to 0
+template <int TIN>
+__device__ __forceinline__ void policy_bwd_delta(const float* __restrict__ wb, const PolicyOp op, const float* hprev,
+                                                 float* dl, const int relu, const bool valid, const int lane) {
+  const int j = lane & 31, h = lane >> 5;
+  pol_f32x16 acc[TIN];
+#pragma unroll
+  for (int ti = 0; ti < TIN; ++ti) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[ti][r] = 0.0f;
+  }
+  for (int to = 0; to < op.tout; ++to) {
+    float b[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) b[s] = dl[(32 * to + 16 * h + s) * POL_XS + j];
+#pragma unroll
+    for (int ti = 0; ti < TIN; ++ti) {
+      const pol_f32x4* wp =
+          reinterpret_cast<const pol_f32x4*>(wb + op.w_off + ((to * 2 * op.nks + 32 * ti + j) * 32 + 16 * h));
+      const pol_f32x4 w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3];
+      const float w[16] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3],
+                           w2[0], w2[1], w2[2], w2[3], w3[0], w3[1], w3[2], w3[3]};
+#pragma unroll
+      for (int s = 0; s < 16; ++s) acc[ti] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[s], b[s], acc[ti], 0, 0, 0);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();  // every read of the delta image is ahead of the writes below
+#pragma unroll
+  for (int ti = 0; ti < TIN; ++ti) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = 32 * ti + pol_unit(r, h);
+      const float hv = hprev[i * POL_XS + j], d = acc[ti][r];
+      const float v = relu ? (hv > 0.0f ? d : 0.0f) : d * (1.0f - hv * hv);
+      dl[i * POL_XS + j] = valid ? v : 0.0f;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <int D>
+__global__ __launch_bounds__(64 * POL_WAVES) void f16_policy_backward_kernel(const PolicyBwdArgs a) {
+  extern __shared__ float4 pol_sm4[];
+  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int j = lane & 31, h = lane >> 5;
+  const float* wb = a.blob;
+  float* xs = reinterpret_cast<float*>(pol_sm4) + wave * a.wave_floats;
+  float* as = xs + a.obs_floats;
+  float* dl = as + a.act_floats;
+  const int64_t slot = (int64_t)blockIdx.x * a.waves + wave;
+  float* g = a.ws + slot * a.blob_floats;
+  pol_f32x16 acc[4];
+  bool first = true;
+  for (int64_t t = slot; t < a.ntiles; t += a.nslots) {
+    const int64_t row0 = t * POL_ROWS;
+    // the tile's 32 rows, flattened (K, D) each, into xs[k * D + d][row]; rows past n - 1 repeat it
+    for (int k = 0; k < a.K; ++k) {
+      const float* fk = a.obs + (int64_t)k * a.frame_stride;
+      for (int e = lane; e < POL_ROWS * D; e += 64) {
+        const int rj = e / D, d = e - rj * D;
+        int64_t row = row0 + rj;
+        row = row < a.n ? row : a.n - 1;
+        xs[(k * D + d) * POL_XS + rj] = fk[row * a.row_stride + d];
+      }
+    }
+    if ((a.in_dim & 1) && lane < POL_ROWS) xs[a.in_dim * POL_XS + lane] = 0.0f;  // the zero-weight pad input
+    __builtin_amdgcn_wave_barrier();
+    const int64_t row = row0 + j;
+    const bool valid = row < a.n;
+
+    for (int br = 0; br < 2; ++br) {
+      const float* dout = br ? a.d_values : a.d_mean;
+      if (!dout) continue;
+      const int base = br * (POL_MAX_LAYERS + 1);
+      const int nl = br ? a.n_vf : a.n_pi;
+      // recompute the branch's activations, layer l into the image at as + 32 POL_XS (tiles below l)
+      {
+        const float* xin = xs;
+        float* hout = as;
+        for (int l = 0; l < nl; ++l) {
+          const PolicyOp op = a.ops[base + l];
+          switch (op.tout) {
+            case 1: policy_bwd_hidden<1>(wb, op, xin, hout, a.relu, lane, acc); break;
+            case 2: policy_bwd_hidden<2>(wb, op, xin, hout, a.relu, lane, acc); break;
+            case 3: policy_bwd_hidden<3>(wb, op, xin, hout, a.relu, lane, acc); break;
+            default: policy_bwd_hidden<4>(wb, op, xin, hout, a.relu, lane, acc); break;
+          }
+          xin = hout;
+          hout += 32 * op.tout * POL_XS;
+        }
+      }
+      // the head's delta: d_mean (units 0..3) or d_values (unit 0) of the rows inside n, zero elsewhere
+      {
+        float dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (valid && h == 0) {
+          if (br == 0) {
+            const float4 m = reinterpret_cast<const float4*>(dout)[row];
+            dv[0] = m.x; dv[1] = m.y; dv[2] = m.z; dv[3] = m.w;
+          } else {
+            dv[0] = dout[row];
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) dl[(16 * h + q) * POL_XS + j] = q < 4 ? dv[q] : 0.0f;
+        __builtin_amdgcn_wave_barrier();
+      }
+      for (int l = nl; l >= 0; --l) {
+        const PolicyOp op = a.ops[base + (l == nl ? POL_MAX_LAYERS : l)];
+        int below = 0;  // tiles of the layers under layer l - 1: where its image starts
+        for (int m = 0; m + 1 < l; ++m) below += a.ops[base + m].tout;
+        const float* xin = l == 0 ? xs : as + 32 * below * POL_XS;
+        switch (op.tout) {
+          case 1: policy_bwd_dw<1>(g, op, xin, dl, first, lane); break;
+          case 2: policy_bwd_dw<2>(g, op, xin, dl, first, lane); break;
+          case 3: policy_bwd_dw<3>(g, op, xin, dl, first, lane); break;
+          default: policy_bwd_dw<4>(g, op, xin, dl, first, lane); break;
+        }
+        policy_bwd_db(g, op, dl, first, lane);
+        if (l == 0) break;  // no gradient to the observation
+        switch (a.ops[base + l - 1].tout) {
+          case 1: policy_bwd_delta<1>(wb, op, xin, dl, a.relu, valid, lane); break;
+          case 2: policy_bwd_delta<2>(wb, op, xin, dl, a.relu, valid, lane); break;
+          case 3: policy_bwd_delta<3>(wb, op, xin, dl, a.relu, valid, lane); break;
+          default: policy_bwd_delta<4>(wb, op, xin, dl, a.relu, valid, lane); break;
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // the next tile's staging follows every read of this one's images
+    first = false;
+  }
+}
+
+// grad[p] = the slices' sum in slot order; +0 at log_std (p >= logstd) and in a branch without an
+// upstream gradient (bit br of skip), whose slices nobody wrote
+__global__ __launch_bounds__(256) void f16_policy_backward_reduce_kernel(const float* __restrict__ ws,
+                                                                         float* __restrict__ grad, const int nf,
+                                                                         const int64_t nact, const int vf0,
+                                                                         const int act_w, const int val_w,
+                                                                         const int logstd, const int skip) {
+  const int p = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (p >= nf) return;
+  const int br = p >= val_w ? 1 : (p >= act_w ? 0 : (p >= vf0 ? 1 : 0));
+  float s = 0.0f;
+  if (p < logstd && !((skip >> br) & 1))
+    for (int64_t k = 0; k < nact; ++k) s += ws[k * nf + p];
+  grad[p] = s;
+}
+
+// ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
 static const char* policy_desc_error(const f16_policy_desc* d) {
@@ -380,6 +631,97 @@ static int policy_forward_impl(void* stream, const f16_policy_desc* desc, const 
   a.logstd_off = (int32_t)off[F16_POLICY_OFF_LOG_STD];
   void* kargs[] = {&a};
   HIPCHK(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * POL_WAVES), kargs, (size_t)lds, (hipStream_t)stream));
+  return 0;
+}
+
+// The backward's launch shape, from the descriptor alone. LDS per wave: the observation image
+// (K D rounded up to even inputs), the wider branch's activation images (the sum of its widths)
+// and a delta image (the widest layer), all x POL_XS floats; waves per block: the most of 4, 2, 1
+// whose images fit POL_LDS_BYTES. grid = min(ceil(tiles / waves), max_blocks or POL_BWD_BLOCKS).
+struct PolicyBwdPlan {
+  int32_t obs_floats, act_floats, wave_floats, waves;
+  int64_t nf, ntiles, grid;
+};
+static int policy_bwd_plan(const f16_policy_desc* desc, int64_t n, int32_t max_blocks, PolicyBwdPlan* p,
+                           int64_t* off, PolicyOp* ops) {
+  if (const char* m = policy_desc_error(desc)) return set_err(-1, m);
+  if (n < 0) return set_err(-1, "n must be >= 0");
+  if (max_blocks < 0) return set_err(-1, "max_blocks must be >= 0 (0: the default)");
+  p->nf = policy_layout(desc, off, ops);
+  int max_w = 32, sum[2] = {0, 0};
+  for (int l = 0; l < desc->n_pi; ++l) { sum[0] += desc->pi_width[l]; max_w = desc->pi_width[l] > max_w ? desc->pi_width[l] : max_w; }
+  for (int l = 0; l < desc->n_vf; ++l) { sum[1] += desc->vf_width[l]; max_w = desc->vf_width[l] > max_w ? desc->vf_width[l] : max_w; }
+  const int in_dim = desc->K * desc->D;
+  p->obs_floats = (in_dim + (in_dim & 1)) * POL_XS;
+  p->act_floats = (sum[0] > sum[1] ? sum[0] : sum[1]) * POL_XS;
+  p->wave_floats = p->obs_floats + p->act_floats + max_w * POL_XS;
+  const int64_t per_wave = (int64_t)p->wave_floats * 4;
+  if (per_wave > POL_LDS_BYTES) return set_err(-1, "the policy's backward images do not fit the LDS for one wave");
+  p->waves = 4 * per_wave <= POL_LDS_BYTES ? 4 : (2 * per_wave <= POL_LDS_BYTES ? 2 : 1);
+  p->ntiles = n / POL_ROWS + (n % POL_ROWS != 0);
+  const int64_t want = (p->ntiles + p->waves - 1) / p->waves, lim = max_blocks ? max_blocks : POL_BWD_BLOCKS;
+  p->grid = want < lim ? want : lim;
+  return 0;
+}
+
+static int policy_backward_workspace_impl(const f16_policy_desc* desc, int64_t n, int32_t max_blocks, int64_t* bytes_out) {
+  PolicyBwdPlan p;
+  int64_t off[F16_POLICY_N_OFFSETS];
+  if (int rc = policy_bwd_plan(desc, n, max_blocks, &p, off, nullptr)) return rc;
+  if (!bytes_out) return set_err(-1, "null argument");
+  *bytes_out = p.grid * p.waves * p.nf * 4;
+  return 0;
+}
+
+static int policy_backward_impl(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
+                                int64_t row_stride, int64_t frame_stride, const float* d_mean, const float* d_values,
+                                void* workspace, int64_t workspace_bytes, int32_t max_blocks, float* grad_blob) {
+  PolicyBwdArgs a{};
+  PolicyBwdPlan p;
+  int64_t off[F16_POLICY_N_OFFSETS];
+  if (int rc = policy_bwd_plan(desc, n, max_blocks, &p, off, a.ops)) return rc;
+  if (n > 0) {
+    if (!blob || !obs || !workspace || !grad_blob) return set_err(-1, "null argument");
+    if (!d_mean && !d_values) return set_err(-1, "d_mean and d_values are both NULL");
+    if (((uintptr_t)blob & 15) != 0 || ((uintptr_t)grad_blob & 15) != 0 || ((uintptr_t)d_mean & 15) != 0 ||
+        ((uintptr_t)workspace & 15) != 0)
+      return set_err(-1, "blob, grad_blob, d_mean and the workspace must be 16-byte aligned");
+    if (((uintptr_t)obs & 3) != 0 || ((uintptr_t)d_values & 3) != 0)
+      return set_err(-1, "obs and d_values must be float-aligned");
+    if (row_stride < 0 || frame_stride < 0) return set_err(-1, "strides must be non-negative");
+    if (workspace_bytes < p.grid * p.waves * p.nf * 4)
+      return set_err(-1, "the workspace is smaller than f16env_policy_backward_workspace says");
+  }
+  const void* fn = desc->D == 15 ? (const void*)f16_policy_backward_kernel<15> : (const void*)f16_policy_backward_kernel<17>;
+  // (dynamic LDS above 64 KB: opted into once per instance and device, as the forward; n == 0 does only this)
+  static uint64_t prepared[2];
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  const int inst = desc->D == 17 ? 1 : 0;
+  if (dev < 0 || dev >= 64 || !(__atomic_load_n(&prepared[inst], __ATOMIC_ACQUIRE) >> dev & 1)) {
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_BYTES));
+    if (dev >= 0 && dev < 64) __atomic_fetch_or(&prepared[inst], 1ull << dev, __ATOMIC_RELEASE);
+  }
+  if (n == 0) return 0;
+  a.blob = blob; a.obs = obs; a.d_mean = d_mean; a.d_values = d_values;
+  a.ws = static_cast<float*>(workspace);
+  a.n = n; a.row_stride = row_stride; a.frame_stride = frame_stride;
+  a.ntiles = p.ntiles; a.nslots = p.grid * p.waves;
+  a.K = desc->K; a.in_dim = desc->K * desc->D;
+  a.obs_floats = p.obs_floats; a.act_floats = p.act_floats; a.wave_floats = p.wave_floats;
+  a.blob_floats = (int32_t)p.nf;
+  a.n_pi = desc->n_pi; a.n_vf = desc->n_vf;
+  a.relu = desc->activation == F16_POLICY_ACT_RELU ? 1 : 0;
+  a.waves = p.waves;
+  void* kargs[] = {&a};
+  HIPCHK(hipLaunchKernel(fn, dim3((unsigned)p.grid), dim3(64 * p.waves), kargs, (size_t)p.waves * p.wave_floats * 4,
+                         (hipStream_t)stream));
+  const int64_t nact = p.ntiles < a.nslots ? p.ntiles : a.nslots;
+  const int skip = (d_mean ? 0 : 1) | (d_values ? 0 : 2);
+  hipLaunchKernelGGL(f16_policy_backward_reduce_kernel, dim3((unsigned)((p.nf + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, a.ws, grad_blob, (int)p.nf, nact, (int)off[6], (int)off[F16_POLICY_OFF_ACT_W],
+                     (int)off[F16_POLICY_OFF_VAL_W], (int)off[F16_POLICY_OFF_LOG_STD], skip);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 

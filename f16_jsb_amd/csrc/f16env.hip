@@ -3653,6 +3653,17 @@ int f16env_policy_forward(void* stream, const f16_policy_desc* desc, const float
                              values, log_probs, flags);
 }
 
+int f16env_policy_backward_workspace(const f16_policy_desc* desc, int64_t n, int32_t max_blocks, int64_t* bytes_out) {
+  return policy_backward_workspace_impl(desc, n, max_blocks, bytes_out);
+}
+
+int f16env_policy_backward(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
+                           int64_t row_stride, int64_t frame_stride, const float* d_mean, const float* d_values,
+                           void* workspace, int64_t workspace_bytes, int32_t max_blocks, float* grad_blob) {
+  return policy_backward_impl(stream, desc, blob, n, obs, row_stride, frame_stride, d_mean, d_values, workspace,
+                              workspace_bytes, max_blocks, grad_blob);
+}
+
 int f16env_features(void* stream, int64_t n_frames, const float* obs, float* feat) {
   if (n_frames < 0) return set_err(-1, "n_frames must be >= 0");
   if (n_frames == 0) return 0;

@@ -14,6 +14,13 @@ values and log-probs where the caller wants them. It fits `collect_rollout`'s `p
     ...                      # PPO update
     pol.load_state_dict(model.policy.state_dict())   # one copy into the same blob
 
+It also learns in place (f16env_policy_backward): the blob is the parameter, `evaluate_actions`
+is differentiable with respect to it through one backward kernel, and the optimiser runs on it:
+
+    pol.requires_grad_(); opt = torch.optim.Adam(pol.parameters(), lr=3e-4, eps=1e-5)
+    v, log_prob, entropy = pol.evaluate_actions(mb.observations, mb.actions)
+    loss = ...; opt.zero_grad(); loss.backward(); clip_grad_norm_(pol.parameters(), 0.5); opt.step()
+
 No stable_baselines3 import: only its key names. No fallback: without the library it raises.
 """
 from __future__ import annotations
@@ -111,6 +118,72 @@ def pack_blob(desc, pi, vf, act_head, val_head, log_std) -> torch.Tensor:
     return blob
 
 
+def unpack_blob(desc, blob):
+    """The inverse of pack_blob, on the blob's device: (pi, vf, act_head, val_head, log_std) with
+    pi / vf lists of (W[out][in], b[out]) and the heads at their true 4 / 1 rows. Copies, not
+    views. A gradient in blob layout (pol.blob.grad) reads per layer the same way."""
+    off, total = policy_blob_layout(desc)
+    blob = torch.as_tensor(blob).detach()
+    if blob.dim() != 1 or blob.numel() != total:
+        raise ValueError("a blob of %d floats was expected, got shape %s" % (total, tuple(blob.shape)))
+
+    def piece(slot, rows, outs, fan_in):
+        nks = (fan_in + 1) // 2
+        w = blob[off[slot]:off[slot] + (rows // 32) * nks * 64].reshape(rows // 32, nks, 2, 32)
+        w = w.permute(0, 3, 1, 2).reshape(rows, 2 * nks)[:outs, :fan_in]
+        return w.clone(), blob[off[slot + 1]:off[slot + 1] + outs].clone()
+
+    branches = []
+    for b, (widths, n) in enumerate(((desc.pi_width, desc.n_pi), (desc.vf_width, desc.n_vf))):
+        layers, fan_in = [], desc.K * desc.D
+        for l in range(n):
+            layers.append(piece(6 * b + 2 * l, widths[l], widths[l], fan_in))
+            fan_in = widths[l]
+        branches.append(layers)
+    act_head = piece(F16_POLICY_OFF_ACT_W, 32, ACT_DIM, desc.pi_width[desc.n_pi - 1])
+    val_head = piece(F16_POLICY_OFF_VAL_W, 32, 1, desc.vf_width[desc.n_vf - 1])
+    ls = off[F16_POLICY_OFF_LOG_STD]
+    return branches[0], branches[1], act_head, val_head, blob[ls:ls + ACT_DIM].clone()
+
+
+def state_dict_from_layers(pi, vf, act_head, val_head, log_std):
+    """The layers under SB3's ActorCriticPolicy key names (what layers_from_state_dict reads)."""
+    sd = {}
+    for name, layers in (("policy_net", pi), ("value_net", vf)):
+        for i, (w, b) in enumerate(layers):
+            sd["mlp_extractor.%s.%d.weight" % (name, 2 * i)] = w
+            sd["mlp_extractor.%s.%d.bias" % (name, 2 * i)] = b
+    sd["action_net.weight"], sd["action_net.bias"] = act_head
+    sd["value_net.weight"], sd["value_net.bias"] = val_head
+    sd["log_std"] = log_std
+    return sd
+
+
+class _MeanAndValue(torch.autograd.Function):
+    """(mean, values) of the blob at obs: the forward kernel (deterministic: its action is the
+    mean), and f16env_policy_backward as the gradient with respect to the blob."""
+
+    @staticmethod
+    def forward(ctx, blob, obs, pol):
+        ctx.pol = pol
+        ctx.set_materialize_grads(False)  # an unused output's branch is skipped by the kernel, not fed zeros
+        ctx.save_for_backward(blob, obs)  # (torch's version check: a step or env write before backward raises)
+        return pol._mean_and_value(obs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_mean, d_values):
+        _, obs = ctx.saved_tensors  # (unpacking is the version check; the kernel reads pol.blob, the same storage)
+        pol = ctx.pol
+
+        def dense(g):  # (a broadcast or sliced upstream gradient: one copy makes it the kernel's input)
+            if g is None:
+                return None
+            g = g.contiguous()
+            return g.clone() if g.data_ptr() % 16 else g
+        return pol.backward_blob(obs, dense(d_mean), dense(d_values)), None, None
+
+
 class DevicePolicy:
     """An SB3-shaped actor-critic MLP policy as one HIP launch per forward.
 
@@ -157,7 +230,8 @@ class DevicePolicy:
     def load(self, pi, vf, act_head, val_head, log_std):
         """Repack the weights into the same device blob (after a PPO update): one stream-ordered
         copy; captured graphs and bound pointers stay valid."""
-        self.blob.copy_(pack_blob(self.desc, pi, vf, act_head, val_head, log_std), non_blocking=True)
+        with torch.no_grad():  # (the blob may be a leaf that requires grad)
+            self.blob.copy_(pack_blob(self.desc, pi, vf, act_head, val_head, log_std), non_blocking=True)
         return self
 
     def load_state_dict(self, sd):
@@ -221,6 +295,102 @@ class DevicePolicy:
     def predict(self, obs, deterministic: bool = True):
         """BasePolicy.predict's action for a batch (the mean when deterministic)."""
         return self(obs, deterministic=deterministic)[0]
+
+    # ------------------------------------------------------------------------------------------
+    # learning: the blob is the parameter (f16env_policy_backward writes its gradient in blob layout)
+    def parameters(self):
+        """[blob]: torch.optim.Adam(pol.parameters()) and clip_grad_norm_(pol.parameters(), c) are
+        SB3's optimiser and clipping element for element -- Adam is elementwise, the pads have zero
+        gradient and zero state, and the norm of the packed gradient is the norm of the layers'."""
+        return [self.blob]
+
+    def requires_grad_(self, flag: bool = True):
+        self.blob.requires_grad_(flag)
+        return self
+
+    def state_dict(self):
+        """The blob's layers under SB3's key names (model.policy.load_state_dict(pol.state_dict()))."""
+        return state_dict_from_layers(*unpack_blob(self.desc, self.blob))
+
+    def _backward_fns(self):
+        from ._lib import F16EnvError, lib
+        L = lib()
+        ws, bwd = getattr(L, "f16env_policy_backward_workspace", None), getattr(L, "f16env_policy_backward", None)
+        if ws is None or bwd is None:
+            raise F16EnvError("this libf16env.so has no f16env_policy_backward: rebuild it (python -m f16_jsb_amd.build)")
+        return ws, bwd
+
+    def reserve_backward(self, n: int, max_blocks: int = 0):
+        """Size the cached workspace for gradients of up to n rows and prepare the kernel instance
+        (call it ahead of a stream capture: nothing may be allocated inside one)."""
+        from ._lib import check
+        ws_fn, bwd = self._backward_fns()
+        need = ctypes.c_int64(0)
+        check(ws_fn(self._desc_ref, int(n), int(max_blocks), ctypes.byref(need)), "f16env_policy_backward_workspace")
+        have = getattr(self, "_bwd_ws", None)
+        if have is None or have.numel() < need.value:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the backward workspace must grow inside a stream capture: call "
+                                   "reserve_backward(n, max_blocks) ahead of it")
+            self._bwd_ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                check(bwd(None, self._desc_ref, None, 0, None, 0, 0, None, None, None, 0, int(max_blocks), None),
+                      "f16env_policy_backward")
+        return self._bwd_ws
+
+    def backward_blob(self, obs, d_mean=None, d_values=None, max_blocks: int = 0, out=None):
+        """sum over rows of d_mean . d mean / d blob + d_values d value / d blob as a tensor in blob
+        layout (two launches; pads and log_std slots +0). d_mean (n, 4) 16-B aligned, d_values (n,),
+        contiguous float32 on the device, either may be None (that branch's gradient is zero)."""
+        from ._lib import check
+        n = self._check_obs(obs)
+        if obs.requires_grad:
+            raise ValueError("no gradient is formed with respect to obs: pass a tensor that does not require grad")
+        if d_mean is None and d_values is None:
+            raise ValueError("d_mean and d_values are both None")
+        if d_mean is not None:
+            self._check_out(d_mean, (n, ACT_DIM), "d_mean", 16)
+        if d_values is not None:
+            self._check_out(d_values, (n,), "d_values", 4)
+        if out is None:
+            out = torch.empty(self.n_floats, dtype=torch.float32, device=self.device)
+        else:
+            self._check_out(out, (self.n_floats,), "out", 16)
+        if n == 0:
+            return out.zero_()
+        ws = self.reserve_backward(n, max_blocks)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        check(self._backward_fns()[1](stream, self._desc_ref, self.blob.data_ptr(), n, obs.data_ptr(), obs.stride(0),
+                                      obs.stride(1), None if d_mean is None else d_mean.data_ptr(),
+                                      None if d_values is None else d_values.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      int(max_blocks), out.data_ptr()), "f16env_policy_backward")
+        return out
+
+    def _mean_and_value(self, obs):
+        n = self._check_obs(obs)
+        mean = torch.empty((n, ACT_DIM), dtype=torch.float32, device=self.device)
+        values = torch.empty(n, dtype=torch.float32, device=self.device)
+        log_probs = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._launch(obs, n, 0, None, mean, values, log_probs, F16_POLICY_DETERMINISTIC)
+        return mean, values
+
+    def mean_and_value(self, obs):
+        """(mean (n, 4), values (n,)), differentiable with respect to the blob when it requires
+        grad (the backward is one kernel, once differentiable); without grad mode just the forward."""
+        if isinstance(obs, torch.Tensor) and obs.requires_grad:
+            raise ValueError("no gradient is formed with respect to obs: pass a tensor that does not require grad")
+        if not (torch.is_grad_enabled() and self.blob.requires_grad):
+            return self._mean_and_value(obs)
+        return _MeanAndValue.apply(self.blob, obs, self)
+
+    def evaluate_actions(self, obs, actions):
+        """ActorCriticPolicy.evaluate_actions for the DiagGaussianDistribution (policies.py,
+        distributions.py): (values (n,), log_prob (n,), entropy (n,)). log_std is a view of the
+        blob, so its gradient reaches blob.grad through autograd's own slice backward."""
+        mean, values = self.mean_and_value(obs)
+        ls = self.offsets[F16_POLICY_OFF_LOG_STD]
+        dist = torch.distributions.Normal(mean, torch.ones_like(mean) * self.blob[ls:ls + ACT_DIM].exp())
+        return values, dist.log_prob(actions).sum(dim=1), dist.entropy().sum(dim=1)
 
 
 def _describe(x):

@@ -64,7 +64,9 @@ extern "C" {
  * MLP forward of a rollout as one kernel); nothing else changed.
  * Still 7: new F16RolloutView and f16env_rollout_minibatch (the PPO update's minibatch sampler).
  * A symbol was added and no signature changed, so a caller built against the earlier 7 runs
- * unchanged; a binding that wants the sampler looks the symbol up and reports its absence. */
+ * unchanged; a binding that wants the sampler looks the symbol up and reports its absence.
+ * Still 7: new f16env_policy_backward_workspace and f16env_policy_backward (the gradient of the
+ * policy's mean and value in the blob's layout), bound the same way. */
 #define F16ENV_ABI_VERSION 7
 
 /* Frame layout (jsbsim_gym.py:12-25 STATE_FORMAT + goal, :172-197) */
@@ -572,6 +574,40 @@ int f16env_policy_blob_layout(const f16_policy_desc* desc, int64_t* offsets_out,
 int f16env_policy_forward(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
                           int64_t row_stride, int64_t frame_stride, uint64_t seed, uint64_t step, int64_t id_base,
                           const float* eps, float* actions, float* values, float* log_probs, uint32_t flags);
+
+/* The backward of the two MLPs, so that a PPO update trains on the blob itself (still ABI 7: two
+ * symbols added). With mean (n x 4) and value (n) exactly what f16env_policy_forward computes from
+ * (blob, obs) -- the same k-ordered chains, the same tanh -- and upstream gradients d_mean (n x 4
+ * float, 16-B aligned) and d_values (n float):
+ *   grad_blob[p] = sum_b ( d_mean[b] . d mean[b] / d blob[p] + d_values[b] d value[b] / d blob[p] )
+ * stored in the blob's own layout (f16env_policy_blob_layout): every weight, bias and head element
+ * where its parameter sits. Every pad position is written as +0, always: the pad input of an odd
+ * fan-in, head rows past 4 / 1, head biases past 4 / 1 and the four log_std slots (mean and value
+ * do not depend on them). The whole of grad_blob[0, n_floats) is overwritten, not accumulated into.
+ * A NULL d_mean (d_values) writes +0 over the pi (vf) branch's pieces and skips its work; both
+ * NULL is an error. Activation derivatives on the recomputed h: tanh 1 - h*h; ReLU h > 0 ? 1 : 0
+ * (0 at 0, as torch). No gradient with respect to obs is formed.
+ *   obs, row_stride, frame_stride   as f16env_policy_forward
+ *   workspace   caller-owned device memory, 16-B aligned, at least the bytes
+ *               f16env_policy_backward_workspace(desc, n, max_blocks) states (a pure host function,
+ *               no device; monotone in n and in max_blocks): the blocks' partial gradients
+ *   max_blocks  limit of the grid; 0: the default (256). grid = min(ceil(n / rows per block),
+ *               limit), rows per block = 32 x the 4, 2 or 1 waves whose LDS images fit 160 KB. A
+ *               wave strides over the row tiles, accumulates its own partial in tile order, and a
+ *               second launch sums the partials in block order.
+ * Determinism: no atomics; the result's bits depend on (desc, n, max_blocks) and the data alone,
+ * and two calls with the same arguments give the same bits. Rows past n - 1 of a last tile
+ * contribute exactly nothing. Nothing outside rows [0, n) of obs, d_mean, d_values is read;
+ * nothing outside grad_blob[0, n_floats) and the stated workspace bytes is written. No handle;
+ * stream-ordered; no sync and no allocation (safe under stream capture, after one call outside
+ * capture -- n == 0 suffices -- has prepared the kernel instance). n == 0 launches nothing and
+ * writes nothing. A bad argument (a bad descriptor, negative n or strides, a NULL or misaligned
+ * pointer, a workspace smaller than stated, max_blocks < 0) returns < 0 with f16env_last_error
+ * set, before any launch. */
+int f16env_policy_backward_workspace(const f16_policy_desc* desc, int64_t n, int32_t max_blocks, int64_t* bytes_out);
+int f16env_policy_backward(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
+                           int64_t row_stride, int64_t frame_stride, const float* d_mean, const float* d_values,
+                           void* workspace, int64_t workspace_bytes, int32_t max_blocks, float* grad_blob);
 
 /* Policy features of every observation frame, replacing
  * jsbsim_gym/features.py:37-67 JSBSimFeatureExtractor.forward (float32):
