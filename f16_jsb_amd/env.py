@@ -1,7 +1,8 @@
 """Host side of the MI355X F-16 environment.
 
 ``F16Envs``   -- thin owner of one libf16env handle: device tensors in, device tensors out
-                 (the throughput path; no per-step allocation, no host sync).
+                 (the throughput path; no per-step allocation, no host sync); what depends on
+                 the observation layout is in layouts.py.
 ``F16VecEnv`` -- drop-in for the reference's VecEnv boundary
                  (stable_baselines3/common/vec_env/base_vec_env.py:50-357 VecEnv ABC,
                  dummy_vec_env.py:56-83 auto-reset / info contract, monitor.py:85-111
@@ -13,20 +14,17 @@ from __future__ import annotations
 
 import ctypes
 import time
-from collections import namedtuple
 from copy import deepcopy
+from functools import partial
 from typing import Any, Optional, Sequence
 
 import numpy as np
 
 from . import spaces
 from ._lib import F16EnvError, check, lib
-from .abi import (RolloutSlot, F16C_N, F16_IC_N, F16_OBS_DIM, F16_FLAG_GUSTS, F16_FLAG_NAN_GUARD, F16_FLAG_NO_AUTORESET,
-                  F16_FLAG_OBS_CHECK, F16_SLOT_CLIP, F16_SLOT_FEATURE_WINDOW, F16_STEP_FEATURE_WINDOW,
-                  F16_STEP_POSES, F16_FLAG_RANDOM_IC,
-                  EnvConfig, algorithmic_bytes_per_env_step, config_default)
-
-StepOut = namedtuple("StepOut", "obs rew terminated truncated terminal_obs ep_return ep_len")
+from .abi import (RolloutSlot, F16C_N, F16_IC_N, F16_OBS_DIM, F16_FLAG_NAN_GUARD, F16_FLAG_NO_AUTORESET,
+                  F16_FLAG_OBS_CHECK, F16_SLOT_CLIP, EnvConfig, algorithmic_bytes_per_env_step, config_default)
+from .layouts import U64, StepOut, _ContiguousLayout, _default_history, _ptr, _WindowLayout, as_act  # noqa: F401
 
 
 def reference_goal(seed) -> np.ndarray:
@@ -42,39 +40,28 @@ def reference_goal(seed) -> np.ndarray:
     return g
 
 
-def _ptr(t) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
-def _default_history(k: int) -> int:
-    """Default window history T (positions per history): max(256, 2K) -- a restart (K-1
-    positions moved to the front) every T-K+1 steps; 2 x 256 x 64 B = 32 KiB per env."""
-    return max(256, 2 * k)
-
-
 class F16Envs:
-    """N F-16 envs on one GPU behind the C ABI. All tensors are torch tensors on ``device``."""
+    """N F-16 envs on one GPU behind the C ABI. All tensors are torch tensors on ``device``. The
+    layout object chosen at creation (layouts.py) owns the observation buffers and their calls."""
 
     def __init__(self, n_envs: int, stack_k: int = 10, device=None, seed: int = 0,
                  env_id_base: int = 0, max_steps: int = 1200, down_sample: int = 4,
                  autoreset: bool = True, ic=None, nan_guard: bool = False, obs_check: bool = False,
-                 obs_layout: str = "contiguous",
-                 history: int = 0, window_order: str = "position", fused_features: bool = False,
-                 fused_poses: bool = False, **cfg_kw):
+                 obs_layout: str = "contiguous", history: int = 0, window_order: str = "position",
+                 fused_features: bool = False, fused_poses: bool = False, **cfg_kw):
         """obs_layout "contiguous": observations in two ping-pong (N, K, 15) buffers (f16env_step).
         obs_layout "window": observations are (N, K, 15) views of two per-env frame histories of
         `history` positions of 64-B frame slots, position-major [T][N][16] (f16env_step_window:
         only the new frame is written per step, one contiguous block per position; view strides
         (16, N*16, 1)); history 0 = max(256, 2K) (a restart every T-K+1 steps); window_order
         "env" keeps the histories env-major [N][T][16] instead (strides (T*16, 16, 1)). Both
-        layouts give identical values and the same validity (an observation stays valid until
-        the step after next). A consumer that needs a flat (N, K*15) array copies the window
-        (reshape); the features kernel (f16_jsb_amd.features) reads it in place.
-        fused_features (windowed layout): every step also keeps the policy features of both
-        windows (obs_features(), features.py:37-67 per frame) in its own epilogue -- the step's
-        feature-window build (f16env_window_step_ex, F16_STEP_FEATURE_WINDOW), no second launch;
-        obs_features() is then a view. Off by default: the plain step's instance carries none of
-        that code.
+        layouts give identical values and the same validity (an observation stays valid until the
+        step after next). A consumer that needs a flat (N, K*15) array copies the window (reshape);
+        the features kernel (f16_jsb_amd.features) reads it in place.
+        fused_features (windowed layout): every step also keeps the policy features of both windows
+        (obs_features(), features.py:37-67 per frame) in its own epilogue (f16env_window_step_ex,
+        F16_STEP_FEATURE_WINDOW), no second launch; obs_features() is then a view. Off by default:
+        the plain step's instance carries none of that code.
         fused_poses (windowed layout): every step also writes the render/telemetry pose of the
         returned observation's newest frame (poses(), telemetry.poses of obs[:, -1], the same
         bits) in its epilogue (f16env_window_step_ex, F16_STEP_POSES): no second launch."""
@@ -86,128 +73,55 @@ class F16Envs:
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise F16EnvError("device must be a cuda (ROCm) device, got %s" % self.device)
-        self.n = int(n_envs)
-        self.k = int(stack_k)
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.n, self.k = n, k = int(n_envs), int(stack_k)
+        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        # the caller's current stream on this device (the raw handle: 0.03 us, where
+        # torch.cuda.current_stream() builds a Stream object per call, ~1.7 us)
         raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        self._raw_stream = raw if raw is not None else (lambda i: torch.cuda.current_stream(i).cuda_stream)
+        self._stream = partial(raw or (lambda i: torch.cuda.current_stream(i).cuda_stream), dev_index)
         flags = int(cfg_kw.pop("flags", 0)) | (0 if autoreset else F16_FLAG_NO_AUTORESET) \
             | (F16_FLAG_NAN_GUARD if nan_guard else 0) | (F16_FLAG_OBS_CHECK if obs_check else 0)
         self.cfg: EnvConfig = config_default(n_envs=n_envs, stack_k=stack_k, seed=seed, env_id_base=env_id_base,
-                                             max_steps=max_steps, down_sample=down_sample, flags=flags, ic=ic,
-                                             **cfg_kw)
-        L = lib()
+                                             max_steps=max_steps, down_sample=down_sample, flags=flags, ic=ic, **cfg_kw)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            check(L.f16env_create(ctypes.byref(self.cfg), self.device.index or 0, ctypes.byref(h)), "f16env_create")
+            check(lib().f16env_create(ctypes.byref(self.cfg), self.device.index or 0, ctypes.byref(h)), "f16env_create")
         self._h = h
         f32, dev = torch.float32, self.device
-        n, k = self.n, self.k
-        if obs_layout not in ("contiguous", "window"):
-            raise ValueError("obs_layout must be 'contiguous' or 'window'")
-        self.window = obs_layout == "window"
-        if self.window:
-            T = int(history) if history else _default_history(k)
-            if T < 2 * k:
-                raise ValueError("history must be >= 2 * stack_k")
-            self.T = T
-            if window_order not in ("position", "env"):
-                raise ValueError("window_order must be 'position' or 'env'")
-            self._env_major = window_order == "env"
-            check(L.f16env_set_window_order(h, 1 if self._env_major else 0), "f16env_set_window_order")
-            # [parity][position][env][16] (64-B frame slots, position-major) or [parity][env][position][16]
-            self._hist = torch.zeros((2, n, T, 16) if self._env_major else (2, T, n, 16), dtype=f32, device=dev)
-            self._hist_ptr = (self._hist[0].data_ptr(), self._hist[1].data_ptr())
-            self._views = [[None] * T for _ in range(2)]
-            self._p = k - 1   # newest frame position of the current observation's window
-            self._obs = None
-            # feature window (obs_features): feature histories beside the frame histories, made
-            # at the first call; op counters tell whether they describe the current windows
-            self._fh = None
-            self._op = 0          # ops that changed the windows (steps, resets, state / obs writes)
-            self._step_op = -1    # the last op that was a step
-            self._feat_op = -1    # the op the feature windows describe
-            self._feat_prev_ok = False  # the feature windows hold the last step's ahead fills
-            self.feature_window_calls = {"incremental": 0, "full": 0, "fused": 0}
-        else:
-            if fused_features or fused_poses:
-                raise ValueError("fused_features / fused_poses need obs_layout='window'")
-            self._obs = [torch.zeros((n, k, F16_OBS_DIM), dtype=f32, device=dev) for _ in range(2)]
-        self.fused_features = bool(fused_features)
-        self.fused_poses = bool(fused_poses)
-        self._poses = None    # (N, 10) pose export; _poses_op: the op it describes
-        self._poses_op = -1
-        self._cur = 0
         # rewards (f32), terminated, truncated (u8) in ONE allocation, so a host-side consumer
         # (F16VecEnv's numpy mode) moves the three with a single device-to-host copy
         nb = (4 * n + 2 * n + 15) // 16 * 16
         self.step_flags = torch.zeros(nb, dtype=torch.uint8, device=dev)
         self.rew = self.step_flags[:4 * n].view(f32)
-        self.term = self.step_flags[4 * n:5 * n]
-        self.trunc = self.step_flags[5 * n:6 * n]
-        # window layout: terminal_obs is re-pointed at the other history's window every step
-        self.terminal_obs = None if self.window else torch.zeros((n, k, F16_OBS_DIM), dtype=f32, device=dev)
+        self.term, self.trunc = self.step_flags[4 * n:5 * n], self.step_flags[5 * n:6 * n]
         self.ep_return = torch.zeros(n, dtype=torch.float64, device=dev)
         self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
         self._act = torch.zeros((n, 4), dtype=f32, device=dev)
-        # the handle's own buffers never move: their addresses are taken once, not per step
+        self.fused_features, self.fused_poses = bool(fused_features), bool(fused_poses)
+        self.window = obs_layout == "window"
+        try:
+            if obs_layout not in ("contiguous", "window"):
+                raise ValueError("obs_layout must be 'contiguous' or 'window'")
+            self._layout = lay = (_WindowLayout if self.window else _ContiguousLayout)(
+                h, self._stream, torch, dev, n, k, self.cfg,
+                (self.rew, self.term, self.trunc, self.ep_return, self.ep_len), history=history,
+                window_order=window_order, fused_features=self.fused_features, fused_poses=self.fused_poses)
+        except Exception:
+            self.close()
+            raise
         if self.window:
-            self._win_ptr = (self.rew.data_ptr(), self.term.data_ptr(), self.trunc.data_ptr(),
-                             self.ep_return.data_ptr(), self.ep_len.data_ptr())
-            self._step_win_fn = L.f16env_step_window
-            check(L.f16env_window_bind(self._h, self._hist_ptr[0], self._hist_ptr[1], self.T, *self._win_ptr),
-                  "f16env_window_bind")
-            self._step_bound = L.f16env_window_step_bound
-            self._step_ex = L.f16env_window_step_ex
-            self.terminal_obs = self._window(1)
-            if (self.fused_features or self.fused_poses) and L.f16env_window_resets_deferred(h):
-                # the deferred-reset step (cfg5 with F16ENV_ICC_PERIOD=0): the epilogue extras
-                # would describe the pre-reset window, and f16env_window_step_ex refuses them --
-                # refused here instead of at the first step
-                self.close()
-                raise ValueError("fused_features / fused_poses are not available with the deferred-reset "
-                                 "windowed step (cfg5 with F16ENV_ICC_PERIOD=0)")
-            if self.fused_features:
-                self._feature_hist()
-            if self.fused_poses:
-                self._poses = torch.zeros((n, 10), dtype=f32, device=dev)
-                check(L.f16env_window_poses_bind(self._h, self._poses.data_ptr()), "f16env_window_poses_bind")
-        else:
-            self._obs_ptr = [o.data_ptr() for o in self._obs]
-            self._out_ptr = (self.rew.data_ptr(), self.term.data_ptr(), self.trunc.data_ptr(),
-                             self.terminal_obs.data_ptr(), self.ep_return.data_ptr(), self.ep_len.data_ptr())
-        self._step_fn = L.f16env_step
+            self.T, self.feature_window_calls = lay.T, lay.derived.calls
+        # the layout's step entry points, bound here: step() pays no attribute hop for them
+        self._step_plain, self._step_rollout_raw = lay.step, lay.step_slot
 
-    # --------------------------------------------------------------------------------------
-    def _stream(self):
-        return ctypes.c_void_p(self._stream_int())
-
-    def _stream_int(self) -> int:
-        """The caller's current stream on this device (the raw handle: 0.03 us, where
-        torch.cuda.current_stream() builds a Stream object per call, ~1.7 us)."""
-        return self._raw_stream(self._dev_index)
-
-    def _window(self, other: int = 0):
-        """(N, K, 15) view of the current (other=0) or other-parity history's window (views are
-        made once per (parity, position) and reused: a step's host cost stays one ctypes call)."""
-        b, p = self._cur ^ other, self._p
-        v = self._views[b][p]
-        if v is None:
-            v = self._views[b][p] = self._make_window(b, p)
-        return v
-
-    def _make_window(self, b: int, p: int):
-        if self._env_major:
-            return self._hist[b, :, p - self.k + 1:p + 1, :F16_OBS_DIM]
-        return self._hist[b, p - self.k + 1:p + 1, :, :F16_OBS_DIM].transpose(0, 1)
-
-    @property
-    def obs(self):
-        return self._window() if self.window else self._obs[self._cur]
+    obs = property(lambda self: self._layout.obs)
+    terminal_obs = property(lambda self: self._layout.terminal_obs)  # (windowed: the other history's window)
 
     def close(self):
-        if getattr(self, "_h", None):
-            lib().f16env_destroy(self._h)
+        h = getattr(self, "_h", None)
+        if h:
+            lib().f16env_destroy(h)
+            h.value = None  # (the layout holds the same object: its calls are refused from here on)
             self._h = None
 
     def __del__(self):
@@ -219,9 +133,7 @@ class F16Envs:
     @property
     def waves_per_simd(self) -> int:
         """Occupancy the step kernel variant of this handle is built for (1 or 2)."""
-        if self.window:
-            return int(lib().f16env_step_window_waves_per_simd(self._h))
-        return int(lib().f16env_step_waves_per_simd(self._h))
+        return self._layout.waves_per_simd
 
     @property
     def step_kernel_name(self) -> str:
@@ -234,8 +146,7 @@ class F16Envs:
 
     def algorithmic_bytes_per_env_step(self) -> int:
         """Bytes per env step of this handle's layout (abi.algorithmic_bytes_per_env_step)."""
-        return algorithmic_bytes_per_env_step(self.k, self.state_bytes_per_env,
-                                              "window" if self.window else "contiguous")
+        return algorithmic_bytes_per_env_step(self.k, self.state_bytes_per_env, self._layout.name)
 
     def stack_bytes_per_env_step(self) -> int:
         """SURVEY.md 8(d)'s B(K): the bytes of the same step with the stack materialised."""
@@ -249,30 +160,22 @@ class F16Envs:
         m = None if mask is None else t.as_tensor(mask, device=self.device).to(t.uint8).contiguous()
         g = None if goals is None else t.as_tensor(goals, device=self.device, dtype=t.float32).contiguous()
         c = None if ic is None else t.as_tensor(ic, device=self.device, dtype=t.float64).contiguous()
-        if m is not None and tuple(m.shape) != (self.n,):
-            raise ValueError("mask must be (N,), got %s" % (tuple(m.shape),))
-        if g is not None and tuple(g.shape) != (self.n, 3):
-            raise ValueError("goals must be (N, 3)")
-        if c is not None and tuple(c.shape) != (self.n, F16_IC_N):
-            raise ValueError("ic must be (N, %d)" % F16_IC_N)
-        if self.window:
-            check(lib().f16env_reset_window(self._h, self._stream(), _ptr(m), _ptr(g), _ptr(c),
-                                            self._hist_ptr[self._cur], self.T, self._p), "f16env_reset_window")
-            self._op += 1
-            return self._window()
-        out = self._obs[self._cur]
-        check(lib().f16env_reset(self._h, self._stream(), _ptr(m), _ptr(g), _ptr(c), _ptr(out)), "f16env_reset")
-        return out
+        for name, x, shape in (("mask", m, (self.n,)), ("goals", g, (self.n, 3)), ("ic", c, (self.n, F16_IC_N))):
+            if x is not None and tuple(x.shape) != shape:
+                raise ValueError("%s must be %s, got %s" % (name, shape, tuple(x.shape)))
+        return self._layout.reset(_ptr(m), _ptr(g), _ptr(c))
 
-    def _need(self, x, shape, dtype, name):
-        """Host-side check of a caller buffer the kernel indexes by env: a wrong shape would be
-        an out-of-bounds access on the device, so it is refused before the launch."""
-        t = self.torch
-        if x is None:
+    def _need(self, x, shape, dtype, name, optional: bool = True):
+        """Host-side check of a caller buffer the kernel indexes by env: a wrong shape, dtype or
+        device would be an out-of-bounds (or host-pointer) access on the device, so it is
+        refused before the launch. Every such buffer goes through here."""
+        if x is None and optional:
             return
-        if not isinstance(x, t.Tensor) or x.device != self.device or x.dtype != dtype or not x.is_contiguous() \
+        if not isinstance(x, self.torch.Tensor) or x.device != self.device or x.dtype != dtype or not x.is_contiguous() \
                 or tuple(x.shape) != tuple(shape):
             raise ValueError("%s must be a contiguous %s %s tensor on %s" % (name, dtype, tuple(shape), self.device))
+
+    _as_act = as_act
 
     def step(self, actions, done_idx=None, n_done=None, features=None, seed=None, step=None) -> StepOut:
         """One env step for all lanes; ``actions`` (N,4) float32 device tensor (or host
@@ -289,115 +192,17 @@ class F16Envs:
                 raise ValueError("actions=None needs seed and step (the in-kernel sample_actions stream)")
             if done_idx is not None or n_done is not None or features is not None:
                 raise ValueError("in-kernel actions: no done list / features argument")
-            if self.window:
-                return self._step_window_ex(None, int(seed), int(step))
-            return self.step_rollout(seed, step)
+            return self._layout.step_ex(None, int(seed), int(step))
         if features is not None:
             return self.step_rollout(0, 0, features=features, policy_actions=actions)
-        if self.window:
-            if (self.fused_features or self.fused_poses) and done_idx is None and n_done is None:
-                return self._step_window_ex(self._as_act(actions), 0, 0)
-            return self._step_window(actions, done_idx, n_done)
-        t = self.torch
-        if done_idx is None and n_done is None and isinstance(actions, t.Tensor) and actions.device == self.device \
-                and actions.dtype == t.float32 and actions.is_contiguous() and actions.shape == (self.n, 4):
-            ap = actions.data_ptr()
-            if ap % 16 == 0:  # the common case: one ctypes call on cached addresses
-                cur = self._cur
-                check(self._step_fn(self._h, self._stream_int(), ap, self._obs_ptr[cur], self._obs_ptr[cur ^ 1],
-                                    *self._out_ptr, None, None), "f16env_step")
-                self._cur = cur ^ 1
-                return StepOut(self._obs[cur ^ 1], self.rew, self.term, self.trunc, self.terminal_obs,
-                               self.ep_return, self.ep_len)
-        if isinstance(actions, t.Tensor) and actions.device == self.device and actions.dtype == t.float32 \
-                and actions.is_contiguous() and actions.data_ptr() % 16 == 0:
-            act = actions
-        else:
-            self._act.copy_(t.as_tensor(actions, dtype=t.float32).reshape(self.n, 4), non_blocking=True)
-            act = self._act
-        if tuple(act.shape) != (self.n, 4):
-            raise ValueError("actions must be (N, 4), got %s" % (tuple(act.shape),))
-        if (done_idx is None) != (n_done is None):
-            raise ValueError("done_idx and n_done go together")
-        self._need(done_idx, (self.n,), t.int32, "done_idx")
-        self._need(n_done, (1,), t.int32, "n_done")
-        prev = self._obs[self._cur]
-        nxt = self._obs[self._cur ^ 1]
-        check(lib().f16env_step(self._h, self._stream(), _ptr(act), _ptr(prev), _ptr(nxt), _ptr(self.rew),
-                                _ptr(self.term), _ptr(self.trunc), _ptr(self.terminal_obs),
-                                _ptr(self.ep_return), _ptr(self.ep_len), _ptr(done_idx), _ptr(n_done)), "f16env_step")
-        self._cur ^= 1
-        return StepOut(nxt, self.rew, self.term, self.trunc, self.terminal_obs, self.ep_return, self.ep_len)
-
-    def _as_act(self, actions):
-        """actions as an aligned contiguous (N, 4) float32 tensor on the device (copied if not)."""
-        t = self.torch
-        if isinstance(actions, t.Tensor) and actions.device == self.device and actions.dtype == t.float32 \
-                and actions.is_contiguous() and actions.data_ptr() % 16 == 0:
-            act = actions
-        else:
-            self._act.copy_(t.as_tensor(actions, dtype=t.float32).reshape(self.n, 4), non_blocking=True)
-            act = self._act
-        if act.shape != (self.n, 4):
-            raise ValueError("actions must be (N, 4), got %s" % (tuple(act.shape),))
-        return act
-
-    def _step_window_ex(self, act, seed: int, step: int) -> StepOut:
-        """f16env_window_step_ex: act None draws the actions in the kernel (sample_actions(seed,
-        step)); a fused_features handle also keeps its feature windows in the step's epilogue
-        whenever they are current before it, and catches them up after a step that could not."""
-        fw = self.fused_features and self._fh is not None and self._feat_prev_ok and self._feat_op == self._op
-        s, cur, p = self._advance()
-        flags = (F16_STEP_FEATURE_WINDOW if fw else 0) | (F16_STEP_POSES if self.fused_poses else 0)
-        check(self._step_ex(self._h, s, None if act is None else act.data_ptr(), cur, p,
-                            flags, seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFFFFFFFFFF), "f16env_window_step_ex")
-        out = self._fused_done(fw, self._advanced(cur, p))
-        if self.fused_poses:
-            self._poses_op = self._op
-        if self.fused_features and not fw:
-            self.obs_features()  # whole windows + the step's ahead fills: the next step fuses
-        return out
-
-    def _step_window(self, actions, done_idx, n_done) -> StepOut:
-        """f16env_step_window: the new frame goes to position p+1 of both histories, the
-        observation is the window ending there in the history of the new parity."""
-        t = self.torch
         act = self._as_act(actions)
-        if done_idx is not None or n_done is not None:
-            if (done_idx is None) != (n_done is None):
-                raise ValueError("done_idx and n_done go together")
-            self._need(done_idx, (self.n,), t.int32, "done_idx")
-            self._need(n_done, (1,), t.int32, "n_done")
-        s, cur, p = self._advance()
-        if done_idx is None:  # the common case: five arguments, the rest bound at creation
-            check(self._step_bound(self._h, s, act.data_ptr(), cur, p), "f16env_window_step_bound")
-        else:
-            check(self._step_win_fn(self._h, s, act.data_ptr(), self._hist_ptr[cur], self._hist_ptr[cur ^ 1], self.T,
-                                    p, *self._win_ptr, _ptr(done_idx), _ptr(n_done)), "f16env_step_window")
-        return self._advanced(cur, p)
-
-    def _advance(self):
-        """(stream, parity, position) of the next windowed step: the new frame goes to position
-        p+1 of both histories (after a restart when p+1 reaches T)."""
-        s = self._stream_int()
-        p = self._p + 1
-        if p >= self.T:  # move the last K-1 frames to the front of both histories
-            check(lib().f16env_window_restart(self._h, s, self._hist_ptr[0], self._hist_ptr[1], self.T, self._p),
-                  "f16env_window_restart")
-            if self._fh is not None and self._feat_op == self._op:  # the feature windows move along
-                k = self.k   # (K-1 whole rows: one contiguous device-to-device copy per parity)
-                for b in (0, 1):
-                    self._fh[b, :k - 1].copy_(self._fh[b, self._p - k + 2:self._p + 1])
-            p = self.k - 1
-        return s, self._cur ^ 1, p
-
-    def _advanced(self, cur, p) -> StepOut:
-        self._cur, self._p = cur, p
-        self._op += 1
-        self._step_op = self._op
-        self.terminal_obs = self._window(1)
-        return StepOut(self._window(), self.rew, self.term, self.trunc, self.terminal_obs, self.ep_return,
-                       self.ep_len)
+        if done_idx is None and n_done is None:  # the common case: one ctypes call on cached addresses
+            return self._step_plain(act)
+        if done_idx is None or n_done is None:
+            raise ValueError("done_idx and n_done go together")
+        self._need(done_idx, (self.n,), self.torch.int32, "done_idx")
+        self._need(n_done, (1,), self.torch.int32, "n_done")
+        return self._step_plain(act, done_idx, n_done)
 
     def step_rollout(self, seed: int, step: int, frame=None, actions=None, rewards=None, next_start=None,
                      policy_actions=None, features=None, next_frame=None, clip: bool = False) -> StepOut:
@@ -407,79 +212,21 @@ class F16Envs:
         layout writes `frame` (the newest frame of the observation acted on), the windowed layout
         `next_frame` (the newest frame of the returned observation, i.e. the next slot's frame).
         policy_actions None: actions drawn in-kernel from the sample_actions(seed, step) stream
-        (bit-identical). clip: the env steps np.clip(policy_actions, low, high) over the action
-        Box (on_policy_algorithm.py:216) while `actions` receives policy_actions unclipped
-        (:247-254)."""
-        t = self.torch
-        act = None
-        if policy_actions is not None:
-            if isinstance(policy_actions, t.Tensor) and policy_actions.device == self.device \
-                    and policy_actions.dtype == t.float32 and policy_actions.is_contiguous() \
-                    and policy_actions.data_ptr() % 16 == 0:
-                act = policy_actions
-            else:
-                self._act.copy_(t.as_tensor(policy_actions, dtype=t.float32).reshape(self.n, 4), non_blocking=True)
-                act = self._act
-            if tuple(act.shape) != (self.n, 4):
-                raise ValueError("policy_actions must be (N, 4), got %s" % (tuple(act.shape),))
-        if self.window and frame is not None:
-            raise ValueError("the windowed layout writes next_frame (the returned observation's newest frame), not frame")
-        if not self.window and next_frame is not None:
-            raise ValueError("the contiguous layout writes frame (the acted-on observation's newest frame), not next_frame")
-        self._need(frame, (self.n, F16_OBS_DIM), t.float32, "frame")
-        self._need(next_frame, (self.n, F16_OBS_DIM), t.float32, "next_frame")
-        self._need(actions, (self.n, 4), t.float32, "actions")
-        self._need(rewards, (self.n,), t.float32, "rewards")
-        self._need(next_start, (self.n,), t.float32, "next_start")
-        if features is not None and (tuple(features.shape) != (self.n, self.k, 17) or features.dtype != t.float32
-                                     or not features.is_contiguous()):
-            raise ValueError("features must be a contiguous float32 (N, K, 17) tensor")
-        slot = RolloutSlot(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, _ptr(frame),
-                           _ptr(actions), _ptr(rewards), _ptr(next_start), _ptr(features), _ptr(next_frame),
-                           F16_SLOT_CLIP if clip else 0, 0)
-        if self.window:
-            fw = self._fused_features(slot)
-            s, cur, p = self._advance()
-            check(lib().f16env_window_step_rollout(self._h, s, ctypes.byref(slot), _ptr(act), cur, p),
-                  "f16env_window_step_rollout")
-            return self._fused_done(fw, self._advanced(cur, p))
-        prev = self._obs[self._cur]
-        nxt = self._obs[self._cur ^ 1]
-        check(lib().f16env_step_rollout(self._h, self._stream(), ctypes.byref(slot), _ptr(act), _ptr(prev), _ptr(nxt),
-                                        _ptr(self.rew), _ptr(self.term), _ptr(self.trunc), _ptr(self.terminal_obs),
-                                        _ptr(self.ep_return), _ptr(self.ep_len), None, None), "f16env_step_rollout")
-        self._cur ^= 1
-        return StepOut(nxt, self.rew, self.term, self.trunc, self.terminal_obs, self.ep_return, self.ep_len)
+        (bit-identical). clip: the env steps np.clip(policy_actions, low, high) over the action Box
+        (on_policy_algorithm.py:216) while `actions` receives policy_actions unclipped (:247-254)."""
+        n, f32 = self.n, self.torch.float32
+        act = None if policy_actions is None else self._as_act(policy_actions, "policy_actions")
+        for name, x, shape in (("frame", frame, (n, F16_OBS_DIM)), ("next_frame", next_frame, (n, F16_OBS_DIM)),
+                               ("actions", actions, (n, 4)), ("rewards", rewards, (n,)),
+                               ("next_start", next_start, (n,)), ("features", features, (n, self.k, 17))):
+            self._need(x, shape, f32, name)
+        slot = RolloutSlot(int(seed) & U64, int(step) & U64, _ptr(frame), _ptr(actions), _ptr(rewards),
+                           _ptr(next_start), _ptr(features), _ptr(next_frame), F16_SLOT_CLIP if clip else 0, 0)
+        return self._layout.step_slot_checked(slot, _ptr(act))
 
-    def _step_rollout_raw(self, slot, act_ptr) -> StepOut:
-        """step_rollout with a prepared RolloutSlot and action address and no argument checks:
-        collect_rollout validates its buffers once per rollout and moves the slot's row
-        addresses itself (the per-step host cost is then the launch, not the checks)."""
-        if self.window:
-            fw = self._fused_features(slot)
-            s, cur, p = self._advance()
-            check(lib().f16env_window_step_rollout(self._h, s, ctypes.byref(slot), act_ptr, cur, p),
-                  "f16env_window_step_rollout")
-            return self._fused_done(fw, self._advanced(cur, p))
-        cur = self._cur
-        nxt = self._obs[cur ^ 1]
-        check(lib().f16env_step_rollout(self._h, self._stream_int(), ctypes.byref(slot), act_ptr, self._obs_ptr[cur],
-                                        self._obs_ptr[cur ^ 1], *self._out_ptr, None, None), "f16env_step_rollout")
-        self._cur = cur ^ 1
-        return StepOut(nxt, self.rew, self.term, self.trunc, self.terminal_obs, self.ep_return, self.ep_len)
-
-    def _fused_features(self, slot) -> bool:
-        """Whether this rollout-slot step keeps the feature window itself (F16_SLOT_FEATURE_WINDOW:
-        the windows are current, so the step's epilogue brings them to its new position)."""
-        fw = self._fh is not None and self._feat_prev_ok and self._feat_op == self._op
-        slot.flags = (slot.flags | F16_SLOT_FEATURE_WINDOW) if fw else (slot.flags & ~F16_SLOT_FEATURE_WINDOW)
-        return fw
-
-    def _fused_done(self, fw: bool, out: StepOut) -> StepOut:
-        if fw:
-            self._feat_op = self._op
-            self.feature_window_calls["fused"] += 1
-        return out
+    # _step_rollout_raw(slot, act_ptr), bound in __init__: step_rollout with a prepared RolloutSlot and
+    # action address and no argument checks -- collect_rollout validates its buffers once per rollout
+    # and moves the slot's row addresses itself (the per-step host cost is the launch, not the checks)
 
     def rollout_random(self, seed: int, step0: int, n_steps: int, frames, actions, rewards, next_start,
                        last_start) -> None:
@@ -493,45 +240,12 @@ class F16Envs:
         is written into both histories at a window beside the current one (when no such window
         fits in the history, the current windows are first moved to its front); no terminal
         observation is kept for the last step's finished lanes."""
-        T = int(n_steps)
-        n = self.n
+        T, n, f32 = int(n_steps), self.n, self.torch.float32
         for name, x, shape in (("frames", frames, (T, n, F16_OBS_DIM)), ("actions", actions, (T, n, 4)),
                                ("rewards", rewards, (T, n)), ("last_start", last_start, (n,))):
-            if x is None or tuple(x.shape) != shape or x.dtype != self.torch.float32 or not x.is_contiguous() \
-                    or x.device != self.device:
-                raise ValueError("%s must be a contiguous float32 %s tensor on %s" % (name, shape, self.device))
-        if T > 1 and (next_start is None or tuple(next_start.shape) != (T - 1, n) or not next_start.is_contiguous()
-                      or next_start.dtype != self.torch.float32 or next_start.device != self.device):
-            raise ValueError("next_start must be a contiguous float32 (T-1, N) tensor")
-        sd, st = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0) & 0xFFFFFFFFFFFFFFFF
-        if self.window:
-            k, p = self.k, self._p
-            q = p + k if p + k < self.T else k - 1  # the output window: beside the input one
-            if q - k + 1 <= p and p - k + 1 <= q:
-                # (T < 3K - 1 and the window near the front, ADVICE r04): move the current windows
-                # of both histories to positions 0 .. K-1 first; the output window K .. 2K-1 then
-                # fits whenever T >= 2K (window_check's bound). The lanes' FRESH marks describe
-                # window-relative positions, so they stay valid.
-                for b in (0, 1):
-                    if self._env_major:
-                        self._hist[b, :, :k].copy_(self._hist[b, :, p - k + 1:p + 1].clone())
-                    else:
-                        self._hist[b, :k].copy_(self._hist[b, p - k + 1:p + 1].clone())
-                p = self._p = k - 1
-                q = 2 * k - 1
-            check(lib().f16env_window_rollout_random(self._h, self._stream(), sd, st, T, self._cur, p, q, _ptr(frames),
-                                                     _ptr(actions), _ptr(rewards), _ptr(next_start), _ptr(last_start)),
-                  "f16env_window_rollout_random")
-            self._p = q
-            self._op += 1
-            self.terminal_obs = self._window(1)
-            return
-        prev = self._obs[self._cur]
-        nxt = self._obs[self._cur ^ 1]
-        check(lib().f16env_rollout_random(self._h, self._stream(), sd, st, T, _ptr(prev), _ptr(nxt), _ptr(frames),
-                                          _ptr(actions), _ptr(rewards), _ptr(next_start), _ptr(last_start)),
-              "f16env_rollout_random")
-        self._cur ^= 1
+            self._need(x, shape, f32, name, optional=False)
+        self._need(next_start, (T - 1, n), f32, "next_start", optional=T == 1)
+        self._layout.rollout_random(int(seed) & U64, int(step0) & U64, T, frames, actions, rewards, next_start, last_start)
 
     def profile_kernel(self, fn, launches: int, times: Optional[list] = None):
         """Run fn() (which issues `launches` steps) with the step kernel's own dispatch events
@@ -550,23 +264,24 @@ class F16Envs:
         check(L.f16env_profile_end(self._h, ctypes.byref(avg), ctypes.byref(mn), ctypes.byref(cnt)), "f16env_profile_end")
         return avg.value, mn.value, cnt.value
 
+    def _count(self, what: str) -> int:
+        c = ctypes.c_uint64()
+        check(getattr(lib(), what)(self._h, self._stream(), ctypes.byref(c)), what)
+        return int(c.value)
+
     @property
     def nonfinite_count(self) -> int:
         """Lanes quarantined by the NaN guard (nan_guard=True) since creation; waits for the
         handle's stream. A quarantined lane ended its step terminated (terminated == 3) with
         reward 0 and was reset."""
-        c = ctypes.c_uint64()
-        check(lib().f16env_nonfinite_count(self._h, self._stream(), ctypes.byref(c)), "f16env_nonfinite_count")
-        return int(c.value)
+        return self._count("f16env_nonfinite_count")
 
     @property
     def obs_bounds_count(self) -> int:
         """Lane-steps since creation whose new observation frame had a finite value outside the
         observation space (obs_check=True; jsbsim_gym.py:268-285's warning, counted on the
         device). Waits for the handle's stream."""
-        c = ctypes.c_uint64()
-        check(lib().f16env_obs_bounds_count(self._h, self._stream(), ctypes.byref(c)), "f16env_obs_bounds_count")
-        return int(c.value)
+        return self._count("f16env_obs_bounds_count")
 
     def get_state(self):
         s = self.torch.zeros((self.n, F16C_N), dtype=self.torch.float64, device=self.device)
@@ -578,36 +293,20 @@ class F16Envs:
         if tuple(s.shape) != (self.n, F16C_N):
             raise ValueError("state must be (N, %d)" % F16C_N)
         check(lib().f16env_set_state(self._h, self._stream(), _ptr(s)), "f16env_set_state")
-        if self.window:
-            self._op += 1
+        self._layout.state_written()
         self.torch.cuda.current_stream(self.device).synchronize()
 
     def set_obs(self, obs):
         """Overwrite the current observation (window layout: both histories' windows, so the
         next step continues from it)."""
-        o = self.torch.as_tensor(obs, dtype=self.torch.float32)
-        if self.window:
-            self._window(0).copy_(o)
-            self._window(1).copy_(o)
-            # both windows are whole now: lanes reset before this need no refill at the next step
-            check(lib().f16env_window_clear_fresh(self._h, self._stream()), "f16env_window_clear_fresh")
-            self._op += 1
-        else:
-            self._obs[self._cur].copy_(o)
+        self._layout.set_obs(self.torch.as_tensor(obs, dtype=self.torch.float32))
 
     def poses(self):
         """(N, 10) float32 render/telemetry poses of the current observation's newest frame
-        (telemetry.poses(self.obs[:, -1]), JSBSimEnv.render, jsbsim_gym.py:381-415). A
-        fused_poses handle's step writes them in its epilogue, so after such a step this is the
-        bound buffer with no launch; otherwise (or after any other op) f16env_poses computes them.
-        The result is a view valid until the next op."""
-        from .telemetry import poses as _poses
-        if self._poses is not None and self._poses_op == getattr(self, "_op", None):
-            return self._poses
-        out = _poses(self.obs, out=self._poses)  # (the newest frame of each stack, read in place)
-        if self._poses is not None:
-            self._poses_op = getattr(self, "_op", None)
-        return out
+        (telemetry.poses(self.obs[:, -1]), JSBSimEnv.render, jsbsim_gym.py:381-415). A fused_poses
+        handle's step writes them in its epilogue, so after such a step this is the bound buffer with
+        no launch; otherwise (or after any other op) f16env_poses computes them. Valid until the next op."""
+        return self._layout.poses()
 
     def obs_features(self):
         """(N, K, 17) float32 policy features of the current observation (features.py:37-67 per
@@ -615,62 +314,11 @@ class F16Envs:
         features.features(self.obs). Windowed layout: kept in two feature histories beside the
         frame histories ([T][N][17] per parity, position-major; the result is a view, valid
         until the first call after the next step, which writes the other parity's rows), so a
-        call after each step transforms one frame per
-        env (f16env_features_window_step) instead of K, and a rollout-slot step (step_rollout,
-        collect_rollout) keeps them in its own epilogue (F16_SLOT_FEATURE_WINDOW: no launch
-        here at all). The first call, a call after a reset,
-        set_state, set_obs or rollout_random, the call after the step that follows one of
-        those, and a call after a step not followed by a call transform both whole windows.
-        Contiguous layout: features(self.obs)."""
-        from .features import FEATURES_DIM, features
-        if not self.window:
-            return features(self.obs)
-        n, k, L = self.n, self.k, lib()
-        self._feature_hist()
-        cur, p = self._cur, self._p
-        if self._feat_op != self._op:
-            wrow, wenv = (16, self.T * 16) if self._env_major else (n * 16, 16)
-            autoreset = 0 if int(self.cfg.flags) & F16_FLAG_NO_AUTORESET else 1
-            s = self._stream()
-            after_step = self._step_op == self._op
-            hc, fc, fo = self._hist_ptr[cur], self._fh_ptr[cur], self._fh_ptr[cur ^ 1]
-            if self._feat_prev_ok and self._feat_op == self._op - 1 and after_step:
-                check(L.f16env_features_window_step(s, n, k, p, hc, wrow, wenv, fc, fo, self.term.data_ptr(),
-                                                    self.trunc.data_ptr(), autoreset, 1),
-                      "f16env_features_window_step")
-                self.feature_window_calls["incremental"] += 1
-            else:
-                self.feature_window_calls["full"] += 1
-                for b in (cur, cur ^ 1):  # positions p-K+1 .. p of history b: K "rows" of N frames
-                    check(L.f16env_features_strided(s, k, n, self._hist_ptr[b] + 4 * (p - k + 1) * wrow, wrow, wenv,
-                                                    self._fh_ptr[b] + 4 * (p - k + 1) * n * FEATURES_DIM),
-                          "f16env_features_strided")
-                # the next step's window fills of the lanes this state's step reset, applied ahead
-                # (f16env_features_window_step's invariant); after any other op the lanes due a
-                # fill are not known here, so the call after the next step transforms whole
-                # windows again
-                self._feat_prev_ok = after_step
-                if after_step:
-                    check(L.f16env_features_window_step(s, n, k, p, hc, wrow, wenv, fc, fo, self.term.data_ptr(),
-                                                        self.trunc.data_ptr(), autoreset, 0),
-                          "f16env_features_window_step")
-            self._feat_op = self._op
-        v = self._fviews[cur][p]
-        if v is None:
-            v = self._fviews[cur][p] = self._fh[cur, p - k + 1:p + 1].transpose(0, 1)
-        return v
-
-    def _feature_hist(self):
-        """The two feature histories [T][N][17] beside the frame histories, allocated and bound
-        once (rollout-slot steps with F16_SLOT_FEATURE_WINDOW and fused_features steps update them
-        in their epilogue); positions outside the window are written before they are read."""
-        if self._fh is None:
-            from .features import FEATURES_DIM
-            t = self.torch
-            self._fh = t.empty((2, self.T, self.n, FEATURES_DIM), dtype=t.float32, device=self.device)
-            self._fh_ptr = (self._fh[0].data_ptr(), self._fh[1].data_ptr())
-            check(lib().f16env_window_feature_bind(self._h, *self._fh_ptr), "f16env_window_feature_bind")
-            self._fviews = [[None] * self.T for _ in range(2)]
+        call after each step transforms one frame per env (f16env_features_window_step) instead
+        of K, and a rollout-slot step (step_rollout, collect_rollout) keeps them in its own
+        epilogue (F16_SLOT_FEATURE_WINDOW: no launch here at all); layouts._Derived says when
+        both whole windows are transformed instead. Contiguous layout: features(self.obs)."""
+        return self._layout.obs_features()
 
     def trim(self, ic):
         t = self.torch
@@ -686,22 +334,12 @@ class F16Envs:
         `steps` = T the (T, N, 4) batches of steps step .. step+T-1 in ONE launch
         (f16env_sample_actions_steps, bit-identical to T single calls)."""
         t = self.torch
-        if steps is None:
-            if out is None:
-                out = t.empty((self.n, 4), dtype=t.float32, device=self.device)
-            if tuple(out.shape) != (self.n, 4) or not out.is_contiguous():
-                raise ValueError("out must be a contiguous (N, 4) float32 tensor")
-            check(lib().f16env_sample_actions(self._h, self._stream(), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                              int(step) & 0xFFFFFFFFFFFFFFFF, _ptr(out)), "f16env_sample_actions")
-            return out
-        T = int(steps)
+        shape = (self.n, 4) if steps is None else (int(steps), self.n, 4)
         if out is None:
-            out = t.empty((T, self.n, 4), dtype=t.float32, device=self.device)
-        if tuple(out.shape) != (T, self.n, 4) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous (steps, N, 4) float32 tensor")
-        check(lib().f16env_sample_actions_steps(self._h, self._stream(), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                int(step) & 0xFFFFFFFFFFFFFFFF, T, _ptr(out)),
-              "f16env_sample_actions_steps")
+            out = t.empty(shape, dtype=t.float32, device=self.device)
+        self._need(out, shape, t.float32, "out")
+        fn = "f16env_sample_actions" if steps is None else "f16env_sample_actions_steps"
+        check(getattr(lib(), fn)(self._h, self._stream(), int(seed) & U64, int(step) & U64, *shape[:-2], _ptr(out)), fn)
         return out
 
 
@@ -764,13 +402,12 @@ class _HostStaging:
         self.i = 0
 
     def actions_to_device(self, actions):
-        """Host actions -> the handle's device action buffer through pinned staging; device
-        float32 (N, 4) tensors pass through untouched."""
+        """Host actions -> the handle's device action buffer through pinned staging; tensors on
+        the device go through as_act (aligned float32 (N, 4) ones untouched)."""
         t, e = self.t, self.envs
         if isinstance(actions, t.Tensor):
-            if actions.device == e.device and actions.dtype == t.float32 and actions.is_contiguous() \
-                    and tuple(actions.shape) == (e.n, 4):
-                return actions
+            if actions.device == e.device and actions.numel() == e.n * 4:
+                return as_act(e, actions.reshape(e.n, 4))
             actions = actions.detach().to("cpu", t.float32).numpy()
         a = np.asarray(actions, dtype=np.float32)
         if a.size != e.n * 4:
@@ -800,7 +437,7 @@ class _HostStaging:
                 e.ep_len.index_select(0, i).cpu().numpy())
 
 
-class _HostWindow:
+class _HostWindow(_HostStaging):
     """Numpy mode over a windowed handle (obs_layout="window", position-major): the host keeps
     a pinned mirror of the device's two frame histories, [2][Th][N][16], and per step copies
     only the step's new 64-B slot block of each (position p of both device histories: 2 x N x 64
@@ -816,21 +453,12 @@ class _HostWindow:
     moves its last K-1 to the front when full."""
 
     def __init__(self, envs: "F16Envs", th: int = 0):
-        t = envs.torch
-        self.t, self.envs = t, envs
-        n, k = envs.n, envs.k
-        self.Th = int(th) if th else max(128, 4 * k)
-        pin = envs.device.type == "cuda"
-        self.H = t.zeros((2, self.Th, n, 16), dtype=t.float32, pin_memory=pin)
+        super().__init__(envs, ring=0)  # (the pinned flags and action staging; no observation ring)
+        self.Th = int(th) if th else max(128, 4 * envs.k)
+        self.H = self.t.zeros((2, self.Th, envs.n, 16), dtype=self.t.float32, pin_memory=envs.device.type == "cuda")
         self.Hn = self.H.numpy()
-        self.flags = t.empty(envs.step_flags.shape, dtype=t.uint8, pin_memory=pin)
-        self.act = t.empty((n, 4), dtype=t.float32, pin_memory=pin)
-        self.par = 0
-        self.q = k - 1
-        self.prev_reset = None
+        self.par, self.q, self.prev_reset = 0, envs.k - 1, None
         self.autoreset = not (int(envs.cfg.flags) & F16_FLAG_NO_AUTORESET)
-
-    actions_to_device = _HostStaging.actions_to_device
 
     def _view(self, par: int) -> np.ndarray:
         k, q = self.envs.k, self.q
@@ -852,9 +480,9 @@ class _HostWindow:
                 self.Hn[b, :k - 1] = self.Hn[b, q - k + 1:q]
             q = k - 1
         par = self.par ^ 1
-        cur, p = e._cur, e._p
-        self.H[par, q].copy_(e._hist[cur, p], non_blocking=True)
-        self.H[par ^ 1, q].copy_(e._hist[cur ^ 1, p], non_blocking=True)
+        new, other = e._layout.new_slots()  # position p of the current and of the other device history
+        self.H[par, q].copy_(new, non_blocking=True)
+        self.H[par ^ 1, q].copy_(other, non_blocking=True)
         self.flags.copy_(e.step_flags, non_blocking=True)
         self.t.cuda.current_stream(e.device).synchronize()
         f = self.flags.numpy()
@@ -884,8 +512,8 @@ class _HostWindow:
 def _staging(envs, copy_obs: bool = False):
     """The numpy-mode staging for a handle: the host window mirror for position-major windowed
     handles (only the new slots cross PCIe), else whole-observation copies."""
-    if getattr(envs, "window", False) and not getattr(envs, "_env_major", True) and hasattr(envs, "_hist") \
-            and not copy_obs:
+    lay = getattr(envs, "_layout", None)  # (a stand-in without a layout: whole-observation copies)
+    if isinstance(lay, _WindowLayout) and not lay.env_major and not copy_obs:
         return _HostWindow(envs)
     return _HostStaging(envs)
 

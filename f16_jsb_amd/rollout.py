@@ -25,6 +25,7 @@ from typing import Dict, Optional
 import torch
 
 from .abi import F16_FLAG_NO_AUTORESET, F16_OBS_DIM, F16_SLOT_CLIP, RolloutSlot, RolloutView
+from .layouts import as_act
 
 FIELDS = ("frames", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns")
 # device memory the deferred timeout bootstrap may take for its stash of terminal observations
@@ -241,11 +242,7 @@ def collect_rollout(envs, buf: DeviceRolloutBuffer, seed: int = 0, step0: int = 
                 act_ptr = act_scratch.data_ptr()
             elif policy_fn is not None:
                 act, v, lp = policy_fn(obs)
-                if not (act.dtype == torch.float32 and act.is_contiguous() and act.shape == (n, 4)
-                        and act.device == dev and act.data_ptr() % 16 == 0):
-                    act = act.reshape(n, 4).to(device=dev, dtype=torch.float32).contiguous()
-                    if act.data_ptr() % 16:
-                        act = act.clone()
+                act = as_act(envs, act.reshape(n, 4), "policy actions")
                 act_ptr = act.data_ptr()
                 buf.values[t].copy_(v.reshape(-1))
                 buf.log_probs[t].copy_(lp.reshape(-1))

@@ -38,9 +38,9 @@ def test_fused_poses_equal_pose_kernel(gpu, c):
         else:
             out = e.step(e.sample_actions(seed=9, step=t))
         resets += int((out.terminated | out.truncated).sum().item())
-        assert e._poses_op == e._op, "the step should have written the pose export"
+        assert e._layout.derived.poses_current(), "the step should have written the pose export"
         fused = e.poses()
-        assert fused.data_ptr() == e._poses.data_ptr()
+        assert fused.data_ptr() == e._layout.poses_buf.data_ptr()
         ref = telemetry.poses(e.obs)
         torch.cuda.synchronize()
         assert torch.equal(fused, ref), "step %d" % t

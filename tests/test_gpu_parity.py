@@ -383,12 +383,12 @@ def test_done_index_compaction(torch_mod):
     act = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
     seen = 0
     for t in range(20):
-        nxt = e._obs[e._cur ^ 1]
+        nxt = e._layout.bufs[e._layout.cur ^ 1]
         rc = L.f16env_step(e._h, stream, act.data_ptr(), e.obs.data_ptr(), nxt.data_ptr(), e.rew.data_ptr(),
                            e.term.data_ptr(), e.trunc.data_ptr(), e.terminal_obs.data_ptr(), e.ep_return.data_ptr(),
                            e.ep_len.data_ptr(), idx.data_ptr(), cnt.data_ptr())
         assert rc == 0
-        e._cur ^= 1
+        e._layout.cur ^= 1
         want = torch.nonzero((e.term | e.trunc).bool()).flatten().cpu().numpy()
         got = np.sort(idx[: int(cnt.item())].cpu().numpy())
         np.testing.assert_array_equal(got, want)
@@ -722,6 +722,41 @@ def test_host_checks_refuse_misshaped_buffers(torch_mod):
     out = g.step(a, done_idx=torch.zeros(n, **i32), n_done=torch.zeros(1, **i32))
     assert torch.isfinite(out.obs).all()
     g.close()
+
+
+@pytest.mark.parametrize("layout", ["contiguous", "window"])
+def test_host_checks_refuse_wrong_dtype_device_and_stride(torch_mod, layout):
+    """Every caller buffer a kernel indexes goes through F16Envs._need (device, dtype, contiguity,
+    shape): a float16 / CPU / non-contiguous sample_actions out (both forms), a float64 rewards or
+    CPU frames in rollout_random and a float16 step_rollout features are refused with ValueError
+    before any launch -- one ordinary step afterwards gives the observation of a fresh handle
+    given the same reset and step."""
+    torch = torch_mod
+    from f16_jsb_amd.env import F16Envs
+    n, k, T = 8, 2, 3
+    f32 = dict(dtype=torch.float32, device="cuda")
+    g, fresh = (F16Envs(n, stack_k=k, seed=4, obs_layout=layout) for _ in range(2))
+    g.reset(), fresh.reset()
+    for steps, shape in ((None, (n, 4)), (T, (T, n, 4))):
+        wide = torch.zeros(shape[:-1] + (8,), **f32)
+        for out in (torch.zeros(shape, dtype=torch.float16, device="cuda"), torch.zeros(shape, dtype=torch.float32),
+                    wide[..., ::2]):
+            assert tuple(out.shape) == shape
+            with pytest.raises(ValueError):
+                g.sample_actions(1, 0, out=out, steps=steps)
+    roll = dict(frames=torch.zeros((T, n, 15), **f32), actions=torch.zeros((T, n, 4), **f32),
+                rewards=torch.zeros((T, n), **f32), next_start=torch.zeros((T - 1, n), **f32),
+                last_start=torch.zeros(n, **f32))
+    with pytest.raises(ValueError):
+        g.rollout_random(1, 0, T, **dict(roll, rewards=torch.zeros((T, n), dtype=torch.float64, device="cuda")))
+    with pytest.raises(ValueError):
+        g.rollout_random(1, 0, T, **dict(roll, frames=torch.zeros((T, n, 15), dtype=torch.float32)))
+    with pytest.raises(ValueError):
+        g.step_rollout(1, 0, features=torch.zeros((n, k, 17), dtype=torch.float16, device="cuda"))
+    a = g.sample_actions(1, 0)
+    assert torch.equal(g.step(a).obs, fresh.step(a).obs)
+    assert torch.equal(g.get_state(), fresh.get_state())
+    g.close(), fresh.close()
 
 
 @pytest.mark.parametrize("layout", ["contiguous", "window"])

@@ -187,7 +187,7 @@ def test_window_rollout_random_shortest_history(gpu, order, warm):
     for t in range(warm):
         act = a.sample_actions(3, t)
         a.step(act), b.step(act)
-    assert k <= b._p <= 2 * k - 2
+    assert k <= b._layout.p <= 2 * k - 2
     outs = []
     for e in (a, b):
         fr = torch.empty((steps, n, 15), dtype=f32, device=gpu)

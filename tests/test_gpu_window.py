@@ -197,7 +197,7 @@ def test_window_views_and_layout(gpu):
     assert tuple(o.shape) == (64, 4, 15) and o.stride() == (16, 64 * 16, 1)
     for t in range(1, 30):  # across a restart
         e.step(e.sample_actions(1, t))
-    assert float(e._hist[..., 15].abs().max()) == 0.0
+    assert float(e._layout.hist[..., 15].abs().max()) == 0.0
     with pytest.raises(ValueError):
         e.rollout_random(0, 0, 2, None, None, None, None, None)
 

@@ -57,13 +57,14 @@ def main(steps=300):
         import ctypes
         from f16_jsb_amd._lib import check, lib
         e.obs_features()
-        wrow, wenv = (16, e.T * 16) if e._env_major else (e.n * 16, 16)
-        cur = e._cur
+        w = e._layout  # the windowed layout: histories, position, parity
+        wrow, wenv = (16, e.T * 16) if w.env_major else (e.n * 16, 16)
+        cur = w.cur
 
         def one():
             check(lib().f16env_features_window_step(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), e.n, k,
-                                                    e._p, e._hist_ptr[cur], wrow, wenv, e._fh_ptr[cur],
-                                                    e._fh_ptr[cur ^ 1], e.term.data_ptr(), e.trunc.data_ptr(), 1, 1),
+                                                    w.p, w.hist_ptr[cur], wrow, wenv, w.fh_ptr[cur],
+                                                    w.fh_ptr[cur ^ 1], e.term.data_ptr(), e.trunc.data_ptr(), 1, 1),
                   "f16env_features_window_step")
 
         def graph_ms():
