@@ -97,6 +97,11 @@ def lib():
     _set(L, "f16env_policy_backward_workspace", [ctypes.POINTER(PolicyDesc), i64, i32, ctypes.POINTER(i64)], i32)
     _set(L, "f16env_policy_backward", [vp, ctypes.POINTER(PolicyDesc), vp, i64, vp, i64, i64, vp, vp, vp, i64, i32, vp],
          i32)
+    # (and for the PPO update's loss head and Adam step: ppo.DevicePPO raises F16EnvError without them)
+    _set(L, "f16env_ppo_workspace", [i64, i32, ctypes.POINTER(i64)], i32)
+    _set(L, "f16env_ppo_head_blocks", [i64, i32, ctypes.POINTER(ctypes.c_int32)], i32)
+    _set(L, "f16env_ppo_loss_head", [vp, i64] + [vp] * 8 + [ctypes.c_uint32, i32, vp, i64, vp, vp], i32)
+    _set(L, "f16env_ppo_adam_step", [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp], i32)
     L.f16env_features.argtypes = [vp, ctypes.c_int64, vp, vp]
     _set(L, "f16env_poses", [vp, ctypes.c_int64, vp, ctypes.c_int64, vp], i32)
     L.f16env_step_kernel_name.argtypes = [vp]
@@ -147,4 +152,5 @@ EXPORTED_SYMBOLS = (
     "f16env_algorithmic_bytes_per_env_step", "f16env_last_error",
     "f16env_policy_blob_layout", "f16env_policy_forward", "f16env_rollout_minibatch",
     "f16env_policy_backward_workspace", "f16env_policy_backward",
+    "f16env_ppo_workspace", "f16env_ppo_head_blocks", "f16env_ppo_loss_head", "f16env_ppo_adam_step",
 )

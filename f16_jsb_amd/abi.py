@@ -191,6 +191,10 @@ F16_POLICY_VALUE_ONLY = 0x2     # the vf branch alone; actions / log_probs not t
 F16_POLICY_N_OFFSETS = 17       # f16env_policy_blob_layout: 6 b + 2 l (+ 1) weight (bias) of layer l, branch b
 F16_POLICY_OFF_ACT_W, F16_POLICY_OFF_ACT_B, F16_POLICY_OFF_VAL_W, F16_POLICY_OFF_VAL_B = 12, 13, 14, 15
 F16_POLICY_OFF_LOG_STD = 16
+F16_PPO_NORMALIZE_ADV = 0x1     # f16env_ppo_loss_head: (A - mean(A)) / (std(A) + 1e-8) when n > 1
+# the device hyper array both PPO kernels read, and f16env_ppo_adam_step's stats (include/f16env.h)
+PPO_HYPER = ("lr", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "beta1", "beta2", "eps")
+PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm", "clip_coef")
 POLICY_WIDTHS = (32, 64, 96, 128)
 POLICY_MAX_LAYERS = 3
 

@@ -2564,6 +2564,7 @@ static EnvArgs env_args(const f16env* h) {
 }
 
 #include "f16_policy.h"
+#include "f16_ppo.h"
 
 extern "C" {
 
@@ -3662,6 +3663,29 @@ int f16env_policy_backward(void* stream, const f16_policy_desc* desc, const floa
                            void* workspace, int64_t workspace_bytes, int32_t max_blocks, float* grad_blob) {
   return policy_backward_impl(stream, desc, blob, n, obs, row_stride, frame_stride, d_mean, d_values, workspace,
                               workspace_bytes, max_blocks, grad_blob);
+}
+
+int f16env_ppo_workspace(int64_t n, int32_t max_blocks, int64_t* bytes_out) {
+  return ppo_workspace_impl(n, max_blocks, bytes_out);
+}
+
+int f16env_ppo_head_blocks(int64_t n, int32_t max_blocks, int32_t* blocks_out) {
+  return ppo_head_blocks_impl(n, max_blocks, blocks_out);
+}
+
+int f16env_ppo_loss_head(void* stream, int64_t n, const float* mean, const float* values, const float* actions,
+                         const float* old_log_prob, const float* advantages, const float* target_values,
+                         const float* log_std, const float* hyper, uint32_t flags, int32_t max_blocks, void* workspace,
+                         int64_t workspace_bytes, float* d_mean, float* d_values) {
+  return ppo_loss_head_impl(stream, n, mean, values, actions, old_log_prob, advantages, target_values, log_std, hyper,
+                            flags, max_blocks, workspace, workspace_bytes, d_mean, d_values);
+}
+
+int f16env_ppo_adam_step(void* stream, int64_t n_floats, float* blob, float* grad_blob, float* exp_avg,
+                         float* exp_avg_sq, int32_t* step, const float* hyper, int64_t log_std_offset,
+                         const void* head_workspace, int32_t head_blocks, float* stats) {
+  return ppo_adam_step_impl(stream, n_floats, blob, grad_blob, exp_avg, exp_avg_sq, step, hyper, log_std_offset,
+                            head_workspace, head_blocks, stats);
 }
 
 int f16env_features(void* stream, int64_t n_frames, const float* obs, float* feat) {

@@ -35,6 +35,10 @@
  *   f16env_policy_forward <- on_policy_algorithm.py:199-202 policy(obs_tensor): common/policies.py
  *                      ActorCriticPolicy.forward with torch_layers.py MlpExtractor's separate pi / vf
  *                      MLPs and a DiagGaussianDistribution, one launch
+ *   f16env_policy_backward <- loss.backward() through those two MLPs (ppo.py:391)
+ *   f16env_ppo_loss_head <- ppo.py:355-388 (the clipped surrogate, value and entropy losses, the
+ *                      statistics) and autograd through them down to (mean, values, log_std)
+ *   f16env_ppo_adam_step <- ppo.py:392-395 clip_grad_norm_ and torch.optim.Adam.step, on the blob
  *   f16env_features <- jsbsim_gym/features.py:37-67 JSBSimFeatureExtractor.forward (8f rank 3)
  *   f16env_features_window_step <- the same per step on a windowed observation, one frame each
  *   f16env_poses    <- jsbsim_gym.py:381-415 JSBSimEnv.render state -> Viewer poses (8f rank 4)
@@ -66,7 +70,10 @@ extern "C" {
  * A symbol was added and no signature changed, so a caller built against the earlier 7 runs
  * unchanged; a binding that wants the sampler looks the symbol up and reports its absence.
  * Still 7: new f16env_policy_backward_workspace and f16env_policy_backward (the gradient of the
- * policy's mean and value in the blob's layout), bound the same way. */
+ * policy's mean and value in the blob's layout), bound the same way.
+ * Still 7: new f16env_ppo_workspace, f16env_ppo_head_blocks, f16env_ppo_loss_head and
+ * f16env_ppo_adam_step (the PPO update between the forward and the new weights), bound the same
+ * way. */
 #define F16ENV_ABI_VERSION 7
 
 /* Frame layout (jsbsim_gym.py:12-25 STATE_FORMAT + goal, :172-197) */
@@ -608,6 +615,92 @@ int f16env_policy_backward_workspace(const f16_policy_desc* desc, int64_t n, int
 int f16env_policy_backward(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
                            int64_t row_stride, int64_t frame_stride, const float* d_mean, const float* d_values,
                            void* workspace, int64_t workspace_bytes, int32_t max_blocks, float* grad_blob);
+
+/* The PPO minibatch update between the forward's (mean, values) and the new weights (still ABI 7:
+ * four symbols added): the loss head, then -- after f16env_policy_backward has turned d_mean and
+ * d_values into the blob's gradient -- gradient clipping and the Adam step, in place on the blob.
+ *
+ * hyper: a DEVICE array of 8 floats both kernels read when they run,
+ *   [F16_PPO_HYPER_LR, _CLIP_RANGE, _ENT_COEF, _VF_COEF, _MAX_GRAD_NORM, _BETA1, _BETA2, _EPS],
+ * so that a captured graph follows a learning-rate or clip-range schedule: the owner updates it
+ * with one stream-ordered 32-byte copy.
+ *
+ * f16env_ppo_loss_head: stable_baselines3/ppo/ppo.py:355-388 for a DiagGaussianDistribution with
+ * a state-independent log_std, and its gradient. Inputs (device, float32, contiguous): mean
+ * (n x 4, 16-B aligned), values (n), actions (n x 4, 16-B aligned), old_log_prob, advantages,
+ * target_values (n each; standard PPO passes its returns), log_std (4 floats, e.g. a pointer into
+ * the blob). Per row b, with c = clip_range, sigma_j = exp(log_std_j):
+ *   lp = sum_j ( -(a_j - mean_j)^2 / (2 sigma_j^2) - log_std_j - log(2 pi) / 2 ),  j = 0 .. 3 in order
+ *   A^ = (A - mean(A)) / (std(A) + 1e-8) with F16_PPO_NORMALIZE_ADV and n > 1 (ppo.py:355), else A;
+ *        mean and unbiased std in fp64 by a launch of their own ahead of the rows
+ *   r = exp(lp - old_log_prob); s1 = A^ r; s2 = A^ clamp(r, 1 - c, 1 + c)
+ *   d surrogate / d r = A^ if 1 - c <= r <= 1 + c or s1 < s2, else exactly 0 (torch.min over
+ *        torch.clamp under autograd); g = -(1 / n) (d surrogate / d r) r
+ *   d_mean[b][j] = g (a_j - mean_j) / sigma_j^2   (a clipped row: +-0 in all four)
+ *   d_values[b]  = vf_coef 2 (values_b - target_values_b) / n
+ * and eight fp64 sums over the rows, one set per block, into the workspace:
+ *   sum_b g (z_bj^2 - 1), z = (a - mean) / sigma, j = 0 .. 3;  sum -min(s1, s2);
+ *   sum (values - target_values)^2;  sum ((r - 1) - log r);  the count of |r - 1| > c.
+ * Row order: blocks of 256 threads; thread t of block k takes rows 256 (k + i grid) + t, i = 0, 1,
+ * ..., and adds them in that order; the block's 256 sums meet in a halving tree (stride 128, 64,
+ * ..., 1). grid = min(ceil(n / 256), max_blocks or 256) = f16env_ppo_head_blocks(n, max_blocks).
+ *   workspace   caller-owned device memory, 8-B aligned, at least f16env_ppo_workspace(n, max_blocks)
+ *               bytes (a pure host function, no device; monotone in n and in max_blocks; 0 for n = 0):
+ *               4 doubles (mean(A), std(A), n, 0) then 8 doubles per block
+ * Where the arithmetic differs from torch's float32: lp, lp - old_log_prob, r = exp(.), A^, s1, s2
+ * and the terms of the eight sums are formed in fp64 from the float32 inputs (log sigma_j is
+ * log_std_j itself, where torch takes log(exp(log_std)); the clip's edges are 1 -+ (double)c); r and
+ * A^ are then rounded to float32 once, and g, d_mean, d_values are float32 from there; the advantage
+ * moments and every sum over rows are fp64 (torch: float32).
+ *
+ * f16env_ppo_adam_step: clip_grad_norm_(max_grad_norm) and torch.optim.Adam's step (no amsgrad, no
+ * weight decay) over blob[0, n_floats), in place, ONE block of 1024 threads.
+ *   head_workspace non-NULL (with head_blocks = f16env_ppo_head_blocks of the head's call): first
+ *     the head's partials are added in block order, grad_blob[log_std_offset + j] = (float)(sum_b g
+ *     (z_bj^2 - 1) - ent_coef) is written for j = 0 .. 3 (the backward leaves +0 there: afterwards
+ *     grad_blob is the complete gradient of the PPO loss), and stats[0..5] = policy_loss, value_loss,
+ *     entropy_loss (= -sum_j (1/2 + log(2 pi)/2 + log_std_j), log_std read from the blob ahead of its
+ *     update), loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss, approx_kl =
+ *     mean((r - 1) - log r), clip_fraction = mean(|r - 1| > c).
+ *   always: total_norm = sqrt(sum g^2) in fp64 (thread t adds g[t]^2, g[t + 1024]^2, ... in index
+ *     order, then the halving tree); coef = min(1, max_grad_norm / (total_norm + 1e-6));
+ *     stats[6] = total_norm (before clipping), stats[7] = coef; per element, g' = g coef:
+ *       m <- m + (1 - beta1) (g' - m);  v <- beta2 v + (1 - beta2) g' g';  t = *step + 1
+ *       p <- p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *     on float32 state with each element's arithmetic in fp64, rounded once per stored value
+ *     (torch: float32 throughout), the two bias corrections from the device step counter, which is
+ *     then stored back as t by an ordinary vector store. grad_blob itself is not scaled. A position
+ *     with g = +0 and m = v = p = +0 (the blob's pads) keeps all bits zero.
+ *   stats   device float[8] or NULL; with head_workspace NULL only [6] and [7] are written
+ *   head_workspace NULL: a plain clipped Adam step over the gradient given (log_std_offset and
+ *     head_blocks are ignored).
+ * Both: no handle; stream-ordered; no sync and no allocation; safe under stream capture. n == 0
+ * (n_floats == 0) launches nothing, writes nothing and leaves *step as it is. Determinism: no
+ * atomics; the bits depend on the arguments and the data alone. Nothing outside rows [0, n),
+ * [0, n_floats), the stated workspace bytes and stats[0, 8) is touched. A bad argument (a NULL or
+ * misaligned pointer, negative n, max_blocks < 0, unknown flags, a workspace smaller than stated,
+ * head_blocks < 1 or log_std_offset outside [0, n_floats - 4] with a head workspace) returns < 0 with
+ * f16env_last_error set, before any launch. */
+#define F16_PPO_NORMALIZE_ADV 0x1
+#define F16_PPO_HYPER_LR 0
+#define F16_PPO_HYPER_CLIP_RANGE 1
+#define F16_PPO_HYPER_ENT_COEF 2
+#define F16_PPO_HYPER_VF_COEF 3
+#define F16_PPO_HYPER_MAX_GRAD_NORM 4
+#define F16_PPO_HYPER_BETA1 5
+#define F16_PPO_HYPER_BETA2 6
+#define F16_PPO_HYPER_EPS 7
+#define F16_PPO_N_HYPER 8
+#define F16_PPO_N_STATS 8
+int f16env_ppo_workspace(int64_t n, int32_t max_blocks, int64_t* bytes_out);
+int f16env_ppo_head_blocks(int64_t n, int32_t max_blocks, int32_t* blocks_out);
+int f16env_ppo_loss_head(void* stream, int64_t n, const float* mean, const float* values, const float* actions,
+                         const float* old_log_prob, const float* advantages, const float* target_values,
+                         const float* log_std, const float* hyper, uint32_t flags, int32_t max_blocks, void* workspace,
+                         int64_t workspace_bytes, float* d_mean, float* d_values);
+int f16env_ppo_adam_step(void* stream, int64_t n_floats, float* blob, float* grad_blob, float* exp_avg,
+                         float* exp_avg_sq, int32_t* step, const float* hyper, int64_t log_std_offset,
+                         const void* head_workspace, int32_t head_blocks, float* stats);
 
 /* Policy features of every observation frame, replacing
  * jsbsim_gym/features.py:37-67 JSBSimFeatureExtractor.forward (float32):
