@@ -24,6 +24,36 @@ def frame_err(a, b):
     return d
 
 
+def edge_ics(n, rng):
+    """Flight-envelope edge ICs in five groups of n // 5 lanes (tests/test_gpu_envelope.py names
+    them; tests/fp32_envelope.py's edge workload draws the same)."""
+    from oracle_ref import default_ic
+    ic = np.tile(default_ic(), (n, 1))
+    q = n // 5
+    # 0: stratosphere and above, transonic to supersonic
+    ic[:q, 2] = rng.uniform(36089.0, 75000.0, q)
+    ic[:q, 3] = rng.uniform(700.0, 2100.0, q)
+    # 1: supersonic at low / mid altitude
+    ic[q:2 * q, 2] = rng.uniform(5000.0, 35000.0, q)
+    ic[q:2 * q, 3] = rng.uniform(1300.0, 2300.0, q)
+    # 2: alpha / beta outside the tables (large w, v body velocities)
+    ic[2 * q:3 * q, 3] = rng.uniform(250.0, 700.0, q)
+    ic[2 * q:3 * q, 4] = rng.uniform(-450.0, 450.0, q)
+    ic[2 * q:3 * q, 5] = rng.uniform(-350.0, 700.0, q)
+    ic[2 * q:3 * q, 2] = rng.uniform(8000.0, 30000.0, q)
+    # 3: inverted / near-vertical attitudes, high body rates
+    ic[3 * q:4 * q, 6] = rng.uniform(-np.pi, np.pi, q)
+    ic[3 * q:4 * q, 7] = rng.uniform(-1.48, 1.48, q)
+    ic[3 * q:4 * q, 9:12] = rng.uniform(-4.0, 4.0, (q, 3))
+    ic[3 * q:4 * q, 2] = rng.uniform(10000.0, 40000.0, q)
+    # 4: just above the 10 m crash floor (jsbsim_gym.py:245), nose down
+    ic[4 * q:, 2] = rng.uniform(40.0, 130.0, n - 4 * q)
+    ic[4 * q:, 7] = rng.uniform(-0.8, -0.3, n - 4 * q)
+    ic[:, 8] = rng.uniform(0.0, 2 * np.pi, n)
+    ic[:, 15] = rng.uniform(0.0, 1.0, n)  # throttle at IC (augmentor above 0.5 x 2)
+    return ic
+
+
 def report(name, err):
     """Max error per frame component as a dict."""
     err = np.asarray(err)

@@ -5,8 +5,8 @@ tests/golden/make_trajectories.py from the CPU oracle on fixed inputs).
   (pins the oracle -- the parity checker -- against drift).
 * GPU: the HIP path on the same inputs matches the committed outputs, read from the fixture
   (no oracle run), within the tolerances of test_gpu_parity.py: done flags bit-exact, rewards
-  within 2e-3, newest frames at the checkpoints within the step / 300-step constant-action /
-  30-step random-action tolerances.
+  within reward_atol of the frame tolerance in force (tests/reward_bound.py), newest frames at
+  the checkpoints within the step / 300-step constant-action / 30-step random-action tolerances.
 Parity against JSBSim itself stays unpinned: the fixture is the restatement's.
 """
 from __future__ import annotations

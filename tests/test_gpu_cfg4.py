@@ -5,7 +5,7 @@ which replaces n_steps iterations of collect_rollouts' env.step + RolloutBuffer.
 (on_policy_algorithm.py:194-262, buffers.py:440-479; the env step is jsbsim_gym.py:199-287).
 
   * oracle parity: the first 30 slots against oracle/f16ref.c stepping the same Philox
-    actions from the same state -- actions and episode starts bit-exact, rewards 2e-3, the
+    actions from the same state -- actions and episode starts bit-exact, rewards reward_atol(TOL_RAND30), the
     slot frames (newest frame of the observation each action acted on) at TOL_RAND30 at slot
     30 and within TOL_STEP at slot 1; a third of the lanes' step counters are staggered so
     they truncate and auto-reset inside the window;

@@ -13,7 +13,7 @@ every lane starts somewhere the kernels take a different path or clamp a table:
 
 Every lane's IC frame and the first eight random-action steps are compared with the fp64
 oracle at the one-step tolerance (growing linearly with the step), done flags bit-exact,
-rewards within 2e-3 -- in the reference task and with cfg5 wind on the same states.
+rewards within the per-lane bound of tests/reward_bound.py -- in the reference task and with cfg5 wind on the same states.
 """
 from __future__ import annotations
 
@@ -22,7 +22,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from oracle_ref import OracleEnvs, default_ic  # noqa: E402
+from oracle_ref import OracleEnvs  # noqa: E402
+from parity_tools import edge_ics as _edge_ics  # noqa: E402
 from parity_tools import frame_err  # noqa: E402
 from reward_bound import RewardChecker  # noqa: E402
 from test_gpu_parity import TOL_STEP  # noqa: E402
@@ -39,33 +40,6 @@ def _assert_frames(gpu, ref, tol, what):
         idx = tuple(np.argwhere(bad)[0])
         raise AssertionError("%s: component %d err %.3e > tol %.1e (gpu %r ref %r)" % (
             what, idx[-1], err[idx], lim[idx], gpu[idx[:-1]], ref[idx[:-1]]))
-
-
-def _edge_ics(n, rng):
-    ic = np.tile(default_ic(), (n, 1))
-    q = n // 5
-    # 0: stratosphere and above, transonic to supersonic
-    ic[:q, 2] = rng.uniform(36089.0, 75000.0, q)
-    ic[:q, 3] = rng.uniform(700.0, 2100.0, q)
-    # 1: supersonic at low / mid altitude
-    ic[q:2 * q, 2] = rng.uniform(5000.0, 35000.0, q)
-    ic[q:2 * q, 3] = rng.uniform(1300.0, 2300.0, q)
-    # 2: alpha / beta outside the tables (large w, v body velocities)
-    ic[2 * q:3 * q, 3] = rng.uniform(250.0, 700.0, q)
-    ic[2 * q:3 * q, 4] = rng.uniform(-450.0, 450.0, q)
-    ic[2 * q:3 * q, 5] = rng.uniform(-350.0, 700.0, q)
-    ic[2 * q:3 * q, 2] = rng.uniform(8000.0, 30000.0, q)
-    # 3: inverted / near-vertical attitudes, high body rates
-    ic[3 * q:4 * q, 6] = rng.uniform(-np.pi, np.pi, q)
-    ic[3 * q:4 * q, 7] = rng.uniform(-1.48, 1.48, q)
-    ic[3 * q:4 * q, 9:12] = rng.uniform(-4.0, 4.0, (q, 3))
-    ic[3 * q:4 * q, 2] = rng.uniform(10000.0, 40000.0, q)
-    # 4: just above the 10 m crash floor (jsbsim_gym.py:245), nose down
-    ic[4 * q:, 2] = rng.uniform(40.0, 130.0, n - 4 * q)
-    ic[4 * q:, 7] = rng.uniform(-0.8, -0.3, n - 4 * q)
-    ic[:, 8] = rng.uniform(0.0, 2 * np.pi, n)
-    ic[:, 15] = rng.uniform(0.0, 1.0, n)  # throttle at IC (augmentor above 0.5 x 2)
-    return ic
 
 
 @pytest.mark.parametrize("cfg5", [False, True], ids=["reference_task", "cfg5_wind"])

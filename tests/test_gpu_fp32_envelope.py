@@ -12,10 +12,15 @@ amplification of fp32-level differences; a systematic defect would leave it earl
 
 Assertion, per frame component c (lat*R .. psi) and horizon t in HORIZONS, over the lanes still
 running on both sides (p99 over lanes):
-    p99_hip(c, t) <= FACTOR * max(p99_ulp1(c, t), p99_round(c, t)) + TOL_RAND30[c]
+    p99_hip(c, t) <= FACTOR * max(p99_ulp1(c, t), p99_round(c, t)) + (TOL_RAND30[c] if t <= 30 else 0)
 (TOL_RAND30, the 30-step frame tolerance, is the floor where the envelope is still below the
-fp32 arithmetic's own per-step rounding: t <= 30). The numbers behind the assertion are
-written to $F16_ENVELOPE_JSON when set (profiles/r06_fp32_envelope.json)."""
+fp32 arithmetic's own per-step rounding: t <= 30, and only there). Up to step 30 that floor is
+nearly the whole bound, so of these horizons only step 100 tests the physics; the 300 and 1199 rows
+are saturated -- both sides are decorrelated there (the envelope's phi p99 is 0.74 rad at 300, 24
+lanes are left at 1199) -- and assert nothing about the physics: they are kept as a record. The
+check with teeth is tests/test_gpu_trajectory_envelope.py: every step 1 .. 120, every step-kernel
+instance, the number format as the only floor. The numbers behind the assertion are written to
+$F16_ENVELOPE_JSON when set (profiles/r06_fp32_envelope.json)."""
 from __future__ import annotations
 
 import json
@@ -32,6 +37,7 @@ from test_gpu_parity import TOL_RAND30  # noqa: E402
 
 HORIZONS = (1, 10, 30, 100, 300, 1199)
 FACTOR = 3.0
+FLOOR_UNTIL = 30
 
 
 @pytest.mark.parametrize("cfg5", [False, True], ids=["reference_task", "cfg5"])
@@ -49,7 +55,7 @@ def test_hip_divergence_within_fp32_envelope(gpu, cfg5):
         for c, nm in enumerate(FRAME_NAMES[:12]):
             env = max(out["ulp1"][t][nm][1], out["round"][t][nm][1])
             hip = out["hip"][t][nm][1]
-            bound = FACTOR * env + TOL_RAND30[c]
+            bound = FACTOR * env + (TOL_RAND30[c] if t <= FLOOR_UNTIL else 0.0)
             row[nm] = {"hip_p99": hip, "envelope_p99": env, "bound": bound,
                        "ratio_to_envelope": hip / env if env > 0 else None}
             worst[(t, nm)] = (hip, bound)
@@ -60,7 +66,7 @@ def test_hip_divergence_within_fp32_envelope(gpu, cfg5):
     if path:
         with open(path, "w") as f:
             json.dump({"test": "tests/test_gpu_fp32_envelope.py", "factor": FACTOR,
-                       "floor": dict(zip(FRAME_NAMES[:12], map(float, TOL_RAND30[:12]))),
+                       "floor": dict(zip(FRAME_NAMES[:12], map(float, TOL_RAND30[:12]))), "floor_until_step": FLOOR_UNTIL,
                        "table": {str(t): r for t, r in table.items()},
                        "raw": {v: {str(t): d for t, d in per.items()} for v, per in out.items()}}, f, indent=1)
     for t in HORIZONS:

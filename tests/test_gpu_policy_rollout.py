@@ -13,7 +13,7 @@ starts / next frame written by the step kernel) and f16env_bootstrap_timeouts. C
   * at cfg4's per-GPU share (32 768 envs, K = 4), with a deterministic torch policy whose
     actions leave the Box, 30 steps against the oracle stepping np.clip of the same actions:
     stored actions / values / log-probs equal the policy's outputs bit for bit, done flags and
-    episode starts bit-exact, raw rewards 2e-3, slot frames TOL_RAND30, the bootstrapped
+    episode starts bit-exact, raw rewards reward_atol(TOL_RAND30), slot frames TOL_RAND30, the bootstrapped
     rewards bit-exact against a numpy restatement of :236-245 on the step's raw rewards and
     terminal values, and the GAE bit-exact against buffers.py:403-438 restated in numpy;
   * the windowed fused rollout is bit-identical to the contiguous one, and the persistent
@@ -294,7 +294,7 @@ def test_persistent_window_rollout_vs_oracle(gpu, k, cfg5):
     """The one-launch windowed rollout (f16env_window_rollout_random) against the oracle stepping
     the same Philox actions: the reference's K = 10, and cfg5 (random-IC resets: a lane's first
     from the reset cache, later ones by its own RunIC in the kernel; gusts). 30 slots with a
-    third of the lanes truncating: actions and episode starts bit-exact, rewards 2e-3, slot
+    third of the lanes truncating: actions and episode starts bit-exact, rewards reward_atol of the frame tolerance, slot
     frames at TOL_RAND30 (cfg5: 99.9 % of the lanes, every lane within 10x, as the cfg5
     production test), the final observation continuing the rebuilt stack."""
     import torch
