@@ -21,12 +21,81 @@ class F16EnvError(RuntimeError):
     pass
 
 
-def _set(L, name, argtypes, restype):
-    """Declare an entry point; tolerate its absence in an older build (tools/variant_sweep.py
-    times earlier libraries side by side -- tests check the product exports every symbol)."""
-    f = getattr(L, name, None)
-    if f is not None:
-        f.argtypes, f.restype = argtypes, restype
+_vp, _i32, _u32, _i64, _u64, _f64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64,
+                                     ctypes.c_double)
+_str, _P = ctypes.c_char_p, ctypes.POINTER
+_cfg, _slot, _view, _desc = _P(EnvConfig), _P(RolloutSlot), _P(RolloutView), _P(PolicyDesc)
+
+# Every entry point of include/f16env.h, in the header's order: name -> (restype, one type per
+# parameter). This table is the binding: lib() applies it, EXPORTED_SYMBOLS is its keys, and
+# tests/test_abi_cpu.py holds it against the header's prototypes (count, class and width of every
+# parameter, the return type). An entry point is added in the header and here, nowhere else.
+SIGNATURES = {
+    "f16env_config_default": (_i32, (_cfg,)),
+    "f16env_config_cfg5": (_i32, (_cfg,)),
+    "f16env_create": (_i32, (_cfg, _i32, _P(_vp))),
+    "f16env_destroy": (_i32, (_vp,)),
+    "f16env_step_mode": (_i32, (_vp,)),
+    "f16env_state_bytes": (ctypes.c_size_t, (_vp,)),
+    "f16env_state_bytes_per_env": (_i32, ()),
+    "f16env_reset": (_i32, (_vp, _vp, _vp, _vp, _vp, _vp)),
+    "f16env_step": (_i32, (_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "f16env_step_window": (_i32, (_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "f16env_window_bind": (_i32, (_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp)),
+    "f16env_window_step_bound": (_i32, (_vp, _vp, _vp, _i32, _i32)),
+    "f16env_window_feature_bind": (_i32, (_vp, _vp, _vp)),
+    "f16env_window_poses_bind": (_i32, (_vp, _vp)),
+    "f16env_window_step_ex": (_i32, (_vp, _vp, _vp, _i32, _i32, _u32, _u64, _u64)),
+    "f16env_window_step_ex_kernel_name": (_str, (_vp, _u32)),
+    "f16env_reset_window": (_i32, (_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32)),
+    "f16env_window_restart": (_i32, (_vp, _vp, _vp, _vp, _i64, _i32)),
+    "f16env_set_window_order": (_i32, (_vp, _i32)),
+    "f16env_window_clear_fresh": (_i32, (_vp, _vp)),
+    "f16env_step_window_waves_per_simd": (_i32, (_vp,)),
+    "f16env_step_window_nt": (_i32, (_vp,)),
+    "f16env_window_resets_deferred": (_i32, (_vp,)),
+    "f16env_step_rollout": (_i32, (_vp, _vp, _slot, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "f16env_window_step_rollout": (_i32, (_vp, _vp, _slot, _vp, _i32, _i32)),
+    "f16env_rollout_random": (_i32, (_vp, _vp, _u64, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "f16env_window_rollout_random": (_i32, (_vp, _vp, _u64, _u64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp)),
+    "f16env_bootstrap_timeouts": (_i32, (_vp, _i64, _vp, _vp, _vp, _vp, _f64)),
+    "f16env_bootstrap_stash": (_i32, (_vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64)),
+    "f16env_bootstrap_apply": (_i32, (_vp, _i64, _vp, _vp, _vp, _f64)),
+    "f16env_abi_version": (_i32, ()),
+    "f16env_nonfinite_count": (_i32, (_vp, _vp, _P(_u64))),
+    "f16env_debug_checks": (_i32, (_vp, _vp, _P(_u32))),
+    "f16env_obs_bounds_count": (_i32, (_vp, _vp, _P(_u64))),
+    "f16env_get_state": (_i32, (_vp, _vp, _vp)),
+    "f16env_set_state": (_i32, (_vp, _vp, _vp)),
+    "f16env_trim": (_i32, (_vp, _vp, _vp, _vp, _vp)),
+    "f16env_sample_actions": (_i32, (_vp, _vp, _u64, _u64, _vp)),
+    "f16env_sample_actions_steps": (_i32, (_vp, _vp, _u64, _u64, _i32, _vp)),
+    "f16env_gae": (_i32, (_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp)),
+    "f16env_rollout_minibatch": (_i32, (_vp, _view, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "f16env_policy_blob_layout": (_i32, (_desc, _P(_i64), _P(_i64))),
+    "f16env_policy_forward": (_i32, (_vp, _desc, _vp, _i64, _vp, _i64, _i64, _u64, _u64, _i64, _vp, _vp, _vp, _vp,
+                                     _u32)),
+    "f16env_policy_backward_workspace": (_i32, (_desc, _i64, _i32, _P(_i64))),
+    "f16env_policy_backward": (_i32, (_vp, _desc, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp)),
+    "f16env_ppo_workspace": (_i32, (_i64, _i32, _P(_i64))),
+    "f16env_ppo_head_blocks": (_i32, (_i64, _i32, _P(_i32))),
+    "f16env_ppo_loss_head": (_i32, (_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _vp, _i64, _vp,
+                                    _vp)),
+    "f16env_ppo_adam_step": (_i32, (_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp)),
+    "f16env_features": (_i32, (_vp, _i64, _vp, _vp)),
+    "f16env_features_strided": (_i32, (_vp, _i64, _i32, _vp, _i64, _i64, _vp)),
+    "f16env_features_window_step": (_i32, (_vp, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32)),
+    "f16env_poses": (_i32, (_vp, _i64, _vp, _i64, _vp)),
+    "f16env_step_kernel_name": (_str, (_vp,)),
+    "f16env_step_waves_per_simd": (_i32, (_vp,)),
+    "f16env_step_variant": (_i32, (_vp,)),
+    "f16env_algorithmic_bytes_per_env_step": (_f64, (_i32,)),
+    "f16env_profile_begin": (_i32, (_vp, _i32)),
+    "f16env_profile_end": (_i32, (_vp, _P(_f64), _P(_f64), _P(_i32))),
+    "f16env_profile_times": (_i32, (_vp, _P(_f64), _i32)),
+    "f16env_last_error": (_str, ()),
+}
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
 def lib():
@@ -41,85 +110,12 @@ def lib():
             "libf16env.so not found at %s: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `python -m f16_jsb_amd.build`" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    vp, i32, u64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_size_t
-    L.f16env_config_default.argtypes = [ctypes.POINTER(EnvConfig)]
-    L.f16env_config_cfg5.argtypes = [ctypes.POINTER(EnvConfig)]
-    L.f16env_create.argtypes = [ctypes.POINTER(EnvConfig), i32, ctypes.POINTER(vp)]
-    L.f16env_destroy.argtypes = [vp]
-    L.f16env_state_bytes.argtypes = [vp]
-    L.f16env_state_bytes.restype = sz
-    L.f16env_state_bytes_per_env.restype = i32
-    L.f16env_reset.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.f16env_step.argtypes = [vp] * 13
-    _set(L, "f16env_step_rollout", [vp, vp, ctypes.POINTER(RolloutSlot)] + [vp] * 11, i32)
-    i64 = ctypes.c_int64
-    _set(L, "f16env_step_window", [vp, vp, vp, vp, vp, i64, i32] + [vp] * 7, i32)
-    _set(L, "f16env_reset_window", [vp, vp, vp, vp, vp, vp, i64, i32], i32)
-    _set(L, "f16env_window_restart", [vp, vp, vp, vp, i64, i32], i32)
-    _set(L, "f16env_step_window_waves_per_simd", [vp], i32)
-    _set(L, "f16env_step_mode", [vp], i32)
-    _set(L, "f16env_features_strided", [vp, i64, i32, vp, i64, i64, vp], i32)
-    _set(L, "f16env_features_window_step", [vp, i64, i32, i32, vp, i64, i64, vp, vp, vp, vp, i32, i32], i32)
-    _set(L, "f16env_set_window_order", [vp, i32], i32)
-    _set(L, "f16env_window_clear_fresh", [vp, vp], i32)
-    _set(L, "f16env_window_bind", [vp, vp, vp, i64, vp, vp, vp, vp, vp], i32)
-    _set(L, "f16env_window_step_bound", [vp, vp, vp, i32, i32], i32)
-    _set(L, "f16env_window_feature_bind", [vp, vp, vp], i32)
-    _set(L, "f16env_step_window_nt", [vp], i32)
-    L.f16env_get_state.argtypes = [vp, vp, vp]
-    L.f16env_nonfinite_count.argtypes = [vp, vp, ctypes.POINTER(u64)]
-    _set(L, "f16env_obs_bounds_count", [vp, vp, ctypes.POINTER(u64)], i32)
-    _set(L, "f16env_debug_checks", [vp, vp, ctypes.POINTER(ctypes.c_uint32)], i32)
-    L.f16env_rollout_random.argtypes = [vp, vp, u64, u64, i32] + [vp] * 7
-    _set(L, "f16env_window_rollout_random", [vp, vp, u64, u64, i32, i32, i32, i32] + [vp] * 5, i32)
-    _set(L, "f16env_window_step_rollout", [vp, vp, ctypes.POINTER(RolloutSlot), vp, i32, i32], i32)
-    _set(L, "f16env_window_step_ex", [vp, vp, vp, i32, i32, ctypes.c_uint32, u64, u64], i32)
-    _set(L, "f16env_window_step_ex_kernel_name", [vp, ctypes.c_uint32], ctypes.c_char_p)
-    _set(L, "f16env_window_poses_bind", [vp, vp], i32)
-    _set(L, "f16env_window_resets_deferred", [vp], i32)
-    _set(L, "f16env_sample_actions_steps", [vp, vp, u64, u64, i32, vp], i32)
-    _set(L, "f16env_bootstrap_timeouts", [vp, i64, vp, vp, vp, vp, ctypes.c_double], i32)
-    _set(L, "f16env_bootstrap_stash", [vp, i64, i32, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64], i32)
-    _set(L, "f16env_bootstrap_apply", [vp, i64, vp, vp, vp, ctypes.c_double], i32)
-    _set(L, "f16env_abi_version", [], i32)
-    _set(L, "f16env_policy_blob_layout", [ctypes.POINTER(PolicyDesc), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32)
-    _set(L, "f16env_policy_forward", [vp, ctypes.POINTER(PolicyDesc), vp, i64, vp, i64, i64, u64, u64, i64, vp, vp, vp,
-                                      vp, ctypes.c_uint32], i32)
-    L.f16env_set_state.argtypes = [vp, vp, vp]
-    L.f16env_trim.argtypes = [vp, vp, vp, vp, vp]
-    L.f16env_sample_actions.argtypes = [vp, vp, u64, u64, vp]
-    L.f16env_gae.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, vp, ctypes.c_double,
-                             ctypes.c_double, vp, vp]
-    # bound only when present: an older library named through F16ENV_LIB still loads, and the
-    # sampler (rollout.rollout_minibatch) then raises F16EnvError
-    _set(L, "f16env_rollout_minibatch", [vp, ctypes.POINTER(RolloutView), i64, vp] + [vp] * 6, i32)
-    # (the same for the policy's backward: DevicePolicy's gradient calls raise F16EnvError without it)
-    _set(L, "f16env_policy_backward_workspace", [ctypes.POINTER(PolicyDesc), i64, i32, ctypes.POINTER(i64)], i32)
-    _set(L, "f16env_policy_backward", [vp, ctypes.POINTER(PolicyDesc), vp, i64, vp, i64, i64, vp, vp, vp, i64, i32, vp],
-         i32)
-    # (and for the PPO update's loss head and Adam step: ppo.DevicePPO raises F16EnvError without them)
-    _set(L, "f16env_ppo_workspace", [i64, i32, ctypes.POINTER(i64)], i32)
-    _set(L, "f16env_ppo_head_blocks", [i64, i32, ctypes.POINTER(ctypes.c_int32)], i32)
-    _set(L, "f16env_ppo_loss_head", [vp, i64] + [vp] * 8 + [ctypes.c_uint32, i32, vp, i64, vp, vp], i32)
-    _set(L, "f16env_ppo_adam_step", [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp], i32)
-    L.f16env_features.argtypes = [vp, ctypes.c_int64, vp, vp]
-    _set(L, "f16env_poses", [vp, ctypes.c_int64, vp, ctypes.c_int64, vp], i32)
-    L.f16env_step_kernel_name.argtypes = [vp]
-    L.f16env_step_kernel_name.restype = ctypes.c_char_p
-    _set(L, "f16env_profile_times", [vp, ctypes.POINTER(ctypes.c_double), i32], i32)
-    L.f16env_step_waves_per_simd.argtypes = [vp]
-    L.f16env_step_waves_per_simd.restype = i32
-    _set(L, "f16env_step_variant", [vp], i32)
-    _set(L, "f16env_profile_begin", [vp, i32], i32)
-    _set(L, "f16env_profile_end", [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                   ctypes.POINTER(ctypes.c_int)], i32)
-    L.f16env_algorithmic_bytes_per_env_step.argtypes = [i32]
-    L.f16env_algorithmic_bytes_per_env_step.restype = ctypes.c_double
-    L.f16env_last_error.restype = ctypes.c_char_p
-    for name in ("f16env_config_default", "f16env_config_cfg5", "f16env_create", "f16env_destroy", "f16env_reset",
-                 "f16env_step", "f16env_get_state", "f16env_set_state", "f16env_trim",
-                 "f16env_sample_actions", "f16env_gae", "f16env_features", "f16env_rollout_random"):
-        getattr(L, name).restype = i32
+    # a symbol an older build lacks stays unbound (the A/B tools time earlier libraries side by
+    # side through F16ENV_LIB; fn() reports its absence, tests check the product exports every one)
+    for name, (restype, argtypes) in SIGNATURES.items():
+        f = getattr(L, name, None)
+        if f is not None:
+            f.restype, f.argtypes = restype, argtypes
     # the header's F16ENV_ABI_VERSION must be the library's (a stale build behind a changed
     # signature would be called with the wrong arguments); libraries from before the version
     # export (ABI 2) load only when named explicitly through F16ENV_LIB (tools comparing builds)
@@ -137,20 +133,9 @@ def check(status: int, what: str):
         raise F16EnvError("%s failed (%d): %s" % (what, status, msg.decode() if msg else "?"))
 
 
-# symbols include/f16env.h declares (tests check the .so exports every one of them)
-EXPORTED_SYMBOLS = (
-    "f16env_config_default", "f16env_config_cfg5", "f16env_create", "f16env_destroy", "f16env_state_bytes",
-    "f16env_state_bytes_per_env", "f16env_reset", "f16env_step", "f16env_step_rollout", "f16env_nonfinite_count", "f16env_obs_bounds_count", "f16env_debug_checks", "f16env_rollout_random",
-    "f16env_step_window", "f16env_reset_window", "f16env_window_restart", "f16env_step_window_waves_per_simd",
-    "f16env_step_mode", "f16env_features_strided", "f16env_features_window_step", "f16env_set_window_order", "f16env_window_clear_fresh",
-    "f16env_window_bind", "f16env_window_step_bound", "f16env_window_feature_bind", "f16env_step_window_nt", "f16env_window_step_rollout",
-    "f16env_window_step_ex", "f16env_window_step_ex_kernel_name", "f16env_window_poses_bind",
-    "f16env_window_resets_deferred", "f16env_sample_actions_steps",
-    "f16env_window_rollout_random", "f16env_bootstrap_timeouts", "f16env_bootstrap_stash", "f16env_bootstrap_apply", "f16env_abi_version",
-    "f16env_get_state",
-    "f16env_set_state", "f16env_trim", "f16env_sample_actions", "f16env_gae", "f16env_features", "f16env_poses", "f16env_step_kernel_name", "f16env_step_waves_per_simd", "f16env_step_variant", "f16env_profile_begin", "f16env_profile_end", "f16env_profile_times",
-    "f16env_algorithmic_bytes_per_env_step", "f16env_last_error",
-    "f16env_policy_blob_layout", "f16env_policy_forward", "f16env_rollout_minibatch",
-    "f16env_policy_backward_workspace", "f16env_policy_backward",
-    "f16env_ppo_workspace", "f16env_ppo_head_blocks", "f16env_ppo_loss_head", "f16env_ppo_adam_step",
-)
+def fn(name: str):
+    """The bound entry point `name`, or F16EnvError when the loaded library is an older build without it."""
+    f = getattr(lib(), name, None)
+    if f is None:
+        raise F16EnvError("this libf16env.so has no %s: rebuild it (python -m f16_jsb_amd.build)" % name)
+    return f

@@ -194,6 +194,9 @@ F16_POLICY_OFF_LOG_STD = 16
 F16_PPO_NORMALIZE_ADV = 0x1     # f16env_ppo_loss_head: (A - mean(A)) / (std(A) + 1e-8) when n > 1
 # the device hyper array both PPO kernels read, and f16env_ppo_adam_step's stats (include/f16env.h)
 PPO_HYPER = ("lr", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "beta1", "beta2", "eps")
+(F16_PPO_HYPER_LR, F16_PPO_HYPER_CLIP_RANGE, F16_PPO_HYPER_ENT_COEF, F16_PPO_HYPER_VF_COEF, F16_PPO_HYPER_MAX_GRAD_NORM,
+ F16_PPO_HYPER_BETA1, F16_PPO_HYPER_BETA2, F16_PPO_HYPER_EPS, F16_PPO_N_HYPER) = range(9)
+F16_PPO_N_STATS = 8
 PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm", "clip_coef")
 POLICY_WIDTHS = (32, 64, 96, 128)
 POLICY_MAX_LAYERS = 3
@@ -211,6 +214,11 @@ class PolicyDesc(ctypes.Structure):
         ("activation", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
     ]
+
+
+# the header's struct names and their mirrors (tests/test_abi_cpu.py holds every field's offset and size together)
+STRUCTS = {"f16env_config": EnvConfig, "f16env_rollout_slot": RolloutSlot, "F16RolloutView": RolloutView,
+           "f16_policy_desc": PolicyDesc}
 
 
 def policy_desc(stack_k: int, frame_dim: int, pi_widths, vf_widths, activation="tanh") -> PolicyDesc:

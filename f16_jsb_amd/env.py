@@ -24,6 +24,7 @@ from . import spaces
 from ._lib import F16EnvError, check, lib
 from .abi import (RolloutSlot, F16C_N, F16_IC_N, F16_OBS_DIM, F16_FLAG_NAN_GUARD, F16_FLAG_NO_AUTORESET,
                   F16_FLAG_OBS_CHECK, F16_SLOT_CLIP, EnvConfig, algorithmic_bytes_per_env_step, config_default)
+from .buffers import need_tensor
 from .layouts import U64, StepOut, _ContiguousLayout, _default_history, _ptr, _WindowLayout, as_act  # noqa: F401
 
 
@@ -165,16 +166,6 @@ class F16Envs:
                 raise ValueError("%s must be %s, got %s" % (name, shape, tuple(x.shape)))
         return self._layout.reset(_ptr(m), _ptr(g), _ptr(c))
 
-    def _need(self, x, shape, dtype, name, optional: bool = True):
-        """Host-side check of a caller buffer the kernel indexes by env: a wrong shape, dtype or
-        device would be an out-of-bounds (or host-pointer) access on the device, so it is
-        refused before the launch. Every such buffer goes through here."""
-        if x is None and optional:
-            return
-        if not isinstance(x, self.torch.Tensor) or x.device != self.device or x.dtype != dtype or not x.is_contiguous() \
-                or tuple(x.shape) != tuple(shape):
-            raise ValueError("%s must be a contiguous %s %s tensor on %s" % (name, dtype, tuple(shape), self.device))
-
     _as_act = as_act
 
     def step(self, actions, done_idx=None, n_done=None, features=None, seed=None, step=None) -> StepOut:
@@ -200,8 +191,8 @@ class F16Envs:
             return self._step_plain(act)
         if done_idx is None or n_done is None:
             raise ValueError("done_idx and n_done go together")
-        self._need(done_idx, (self.n,), self.torch.int32, "done_idx")
-        self._need(n_done, (1,), self.torch.int32, "n_done")
+        need_tensor(done_idx, (self.n,), self.torch.int32, self.device, "done_idx")
+        need_tensor(n_done, (1,), self.torch.int32, self.device, "n_done")
         return self._step_plain(act, done_idx, n_done)
 
     def step_rollout(self, seed: int, step: int, frame=None, actions=None, rewards=None, next_start=None,
@@ -219,7 +210,7 @@ class F16Envs:
         for name, x, shape in (("frame", frame, (n, F16_OBS_DIM)), ("next_frame", next_frame, (n, F16_OBS_DIM)),
                                ("actions", actions, (n, 4)), ("rewards", rewards, (n,)),
                                ("next_start", next_start, (n,)), ("features", features, (n, self.k, 17))):
-            self._need(x, shape, f32, name)
+            need_tensor(x, shape, f32, self.device, name, optional=True)
         slot = RolloutSlot(int(seed) & U64, int(step) & U64, _ptr(frame), _ptr(actions), _ptr(rewards),
                            _ptr(next_start), _ptr(features), _ptr(next_frame), F16_SLOT_CLIP if clip else 0, 0)
         return self._layout.step_slot_checked(slot, _ptr(act))
@@ -243,8 +234,8 @@ class F16Envs:
         T, n, f32 = int(n_steps), self.n, self.torch.float32
         for name, x, shape in (("frames", frames, (T, n, F16_OBS_DIM)), ("actions", actions, (T, n, 4)),
                                ("rewards", rewards, (T, n)), ("last_start", last_start, (n,))):
-            self._need(x, shape, f32, name, optional=False)
-        self._need(next_start, (T - 1, n), f32, "next_start", optional=T == 1)
+            need_tensor(x, shape, f32, self.device, name)
+        need_tensor(next_start, (T - 1, n), f32, self.device, "next_start", optional=T == 1)
         self._layout.rollout_random(int(seed) & U64, int(step0) & U64, T, frames, actions, rewards, next_start, last_start)
 
     def profile_kernel(self, fn, launches: int, times: Optional[list] = None):
@@ -337,7 +328,7 @@ class F16Envs:
         shape = (self.n, 4) if steps is None else (int(steps), self.n, 4)
         if out is None:
             out = t.empty(shape, dtype=t.float32, device=self.device)
-        self._need(out, shape, t.float32, "out")
+        need_tensor(out, shape, t.float32, self.device, "out")
         fn = "f16env_sample_actions" if steps is None else "f16env_sample_actions_steps"
         check(getattr(lib(), fn)(self._h, self._stream(), int(seed) & U64, int(step) & U64, *shape[:-2], _ptr(out)), fn)
         return out

@@ -3,7 +3,7 @@ buffers, their cached addresses and the ctypes entry points that take them, and 
 same calls -- obs / terminal_obs, reset, step (with or without a done list), step_ex (in-kernel
 actions, fused features / poses), step_slot(_checked) (the rollout-slot step), rollout_random,
 set_obs, state_written, obs_features, poses, waves_per_simd. Arguments arrive validated
-(F16Envs._need / as_act): nothing here checks a caller's buffer."""
+(buffers.need_tensor / as_act): nothing here checks a caller's buffer."""
 from __future__ import annotations
 
 import ctypes

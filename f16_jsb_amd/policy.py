@@ -32,6 +32,7 @@ import torch
 from .abi import (F16_POLICY_DETERMINISTIC, F16_POLICY_N_OFFSETS, F16_POLICY_OFF_ACT_B, F16_POLICY_OFF_ACT_W,
                   F16_POLICY_OFF_LOG_STD, F16_POLICY_OFF_VAL_B, F16_POLICY_OFF_VAL_W, F16_POLICY_VALUE_ONLY,
                   policy_blob_layout, policy_desc)
+from .buffers import need_tensor, stream_ptr
 
 ACT_DIM = 4
 
@@ -203,6 +204,7 @@ class DevicePolicy:
         self.offsets, self.n_floats = policy_blob_layout(desc)
         self.blob = torch.zeros(self.n_floats, dtype=torch.float32, device=self.device)
         self._desc_ref = ctypes.byref(desc)
+        self._bwd_fns = None
         if self.device.type == "cuda":
             from ._lib import check, lib
             self._fwd = lib().f16env_policy_forward
@@ -246,17 +248,10 @@ class DevicePolicy:
                              % (self.k, self.d, self.device, _describe(obs)))
         return int(obs.shape[0])
 
-    def _check_out(self, x, shape, name, align):
-        if not isinstance(x, torch.Tensor) or x.device != self.device or x.dtype != torch.float32 \
-                or not x.is_contiguous() or tuple(x.shape) != tuple(shape) or x.data_ptr() % align:
-            raise ValueError("%s must be a contiguous %d-byte aligned float32 %s tensor on %s"
-                             % (name, align, tuple(shape), self.device))
-
     def _launch(self, obs, n, step, eps, actions, values, log_probs, flags):
         from ._lib import check
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        check(self._fwd(stream, self._desc_ref, self.blob.data_ptr(), n, obs.data_ptr(), obs.stride(0), obs.stride(1),
-                        self.seed, int(step) & 0xFFFFFFFFFFFFFFFF, self.env_id_base,
+        check(self._fwd(stream_ptr(self.device), self._desc_ref, self.blob.data_ptr(), n, obs.data_ptr(), obs.stride(0),
+                        obs.stride(1), self.seed, int(step) & 0xFFFFFFFFFFFFFFFF, self.env_id_base,
                         None if eps is None else eps.data_ptr(), None if actions is None else actions.data_ptr(),
                         values.data_ptr(), None if log_probs is None else log_probs.data_ptr(), flags),
               "f16env_policy_forward")
@@ -265,11 +260,11 @@ class DevicePolicy:
         """The forward with caller-owned outputs: actions (n, 4) 16-B aligned, values (n,),
         log_probs (n,), contiguous float32 (e.g. rows of a rollout buffer)."""
         n = self._check_obs(obs)
-        self._check_out(actions, (n, ACT_DIM), "actions", 16)
-        self._check_out(values, (n,), "values", 4)
-        self._check_out(log_probs, (n,), "log_probs", 4)
+        need_tensor(actions, (n, ACT_DIM), torch.float32, self.device, "actions", 16)
+        need_tensor(values, (n,), torch.float32, self.device, "values", 4)
+        need_tensor(log_probs, (n,), torch.float32, self.device, "log_probs", 4)
         if eps is not None:
-            self._check_out(eps, (n, ACT_DIM), "eps", 16)
+            need_tensor(eps, (n, ACT_DIM), torch.float32, self.device, "eps", 16)
         self._launch(obs, n, step, eps, actions, values, log_probs, F16_POLICY_DETERMINISTIC if deterministic else 0)
 
     def __call__(self, obs, step=None, eps=None, deterministic=False):
@@ -288,7 +283,7 @@ class DevicePolicy:
         if out is None:
             out = torch.empty(n, dtype=torch.float32, device=self.device)
         else:
-            self._check_out(out, (n,), "out", 4)
+            need_tensor(out, (n,), torch.float32, self.device, "out", 4)
         self._launch(obs, n, 0, None, None, out, None, F16_POLICY_VALUE_ONLY)
         return out
 
@@ -313,12 +308,10 @@ class DevicePolicy:
         return state_dict_from_layers(*unpack_blob(self.desc, self.blob))
 
     def _backward_fns(self):
-        from ._lib import F16EnvError, lib
-        L = lib()
-        ws, bwd = getattr(L, "f16env_policy_backward_workspace", None), getattr(L, "f16env_policy_backward", None)
-        if ws is None or bwd is None:
-            raise F16EnvError("this libf16env.so has no f16env_policy_backward: rebuild it (python -m f16_jsb_amd.build)")
-        return ws, bwd
+        if self._bwd_fns is None:  # (taken at the first gradient: an older library still runs the forward)
+            from ._lib import fn
+            self._bwd_fns = fn("f16env_policy_backward_workspace"), fn("f16env_policy_backward")
+        return self._bwd_fns
 
     def reserve_backward(self, n: int, max_blocks: int = 0):
         """Size the cached workspace for gradients of up to n rows and prepare the kernel instance
@@ -349,19 +342,18 @@ class DevicePolicy:
         if d_mean is None and d_values is None:
             raise ValueError("d_mean and d_values are both None")
         if d_mean is not None:
-            self._check_out(d_mean, (n, ACT_DIM), "d_mean", 16)
+            need_tensor(d_mean, (n, ACT_DIM), torch.float32, self.device, "d_mean", 16)
         if d_values is not None:
-            self._check_out(d_values, (n,), "d_values", 4)
+            need_tensor(d_values, (n,), torch.float32, self.device, "d_values", 4)
         if out is None:
             out = torch.empty(self.n_floats, dtype=torch.float32, device=self.device)
         else:
-            self._check_out(out, (self.n_floats,), "out", 16)
+            need_tensor(out, (self.n_floats,), torch.float32, self.device, "out", 16)
         if n == 0:
             return out.zero_()
         ws = self.reserve_backward(n, max_blocks)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        check(self._backward_fns()[1](stream, self._desc_ref, self.blob.data_ptr(), n, obs.data_ptr(), obs.stride(0),
-                                      obs.stride(1), None if d_mean is None else d_mean.data_ptr(),
+        check(self._backward_fns()[1](stream_ptr(self.device), self._desc_ref, self.blob.data_ptr(), n, obs.data_ptr(),
+                                      obs.stride(0), obs.stride(1), None if d_mean is None else d_mean.data_ptr(),
                                       None if d_values is None else d_values.data_ptr(), ws.data_ptr(), ws.numel(),
                                       int(max_blocks), out.data_ptr()), "f16env_policy_backward")
         return out

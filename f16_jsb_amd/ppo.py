@@ -22,6 +22,7 @@ import ctypes
 import torch
 
 from .abi import F16_POLICY_OFF_LOG_STD, F16_PPO_NORMALIZE_ADV, PPO_HYPER, PPO_STATS
+from .buffers import need_tensor, stream_ptr
 from .policy import ACT_DIM
 
 
@@ -43,17 +44,12 @@ class DevicePPO:
     def __init__(self, pol, lr: float = 3e-4, clip_range: float = 0.2, ent_coef: float = 0.0, vf_coef: float = 0.5,
                  max_grad_norm: float = 0.5, normalize_advantage: bool = True, betas=(0.9, 0.999), eps: float = 1e-5,
                  max_batch: int = 256, max_blocks: int = 0):
-        from ._lib import F16EnvError, lib
+        from ._lib import F16EnvError, fn
         if pol.device.type != "cuda":
             raise F16EnvError("DevicePPO runs on the GPU (f16env_ppo_loss_head, f16env_ppo_adam_step); the policy is "
                               "on %s and there is no fallback" % pol.device)
-        L = lib()
-        names = ("f16env_ppo_workspace", "f16env_ppo_head_blocks", "f16env_ppo_loss_head", "f16env_ppo_adam_step")
-        fns = [getattr(L, name, None) for name in names]
-        if any(f is None for f in fns):
-            raise F16EnvError("this libf16env.so has no f16env_ppo_loss_head / f16env_ppo_adam_step: rebuild it "
-                              "(python -m f16_jsb_amd.build)")
-        self._ws_fn, self._blocks_fn, self._head, self._adam = fns
+        self._ws_fn, self._blocks_fn, self._head, self._adam = map(fn, (
+            "f16env_ppo_workspace", "f16env_ppo_head_blocks", "f16env_ppo_loss_head", "f16env_ppo_adam_step"))
         self.pol, self.device = pol, pol.device
         self.normalize_advantage = bool(normalize_advantage)
         self.max_blocks = int(max_blocks)
@@ -100,9 +96,6 @@ class DevicePPO:
         self.max_batch = n
         return self
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _bump(self):
         if not torch.cuda.is_current_stream_capturing():
             torch.autograd.graph.increment_version(self.pol.blob)
@@ -121,10 +114,10 @@ class DevicePPO:
             observations, actions, old_values, old_log_prob, advantages, returns = observations
         pol = self.pol
         n = pol._check_obs(observations)
-        pol._check_out(actions, (n, ACT_DIM), "actions", 16)
+        need_tensor(actions, (n, ACT_DIM), torch.float32, self.device, "actions", 16)
         for x, name in ((old_values, "old_values"), (old_log_prob, "old_log_prob"), (advantages, "advantages"),
                         (returns, "returns")):
-            pol._check_out(x, (n,), name, 4)
+            need_tensor(x, (n,), torch.float32, self.device, name)
         if n == 0:
             return self
         self.reserve(n)
@@ -132,14 +125,14 @@ class DevicePPO:
         pol.forward_into(observations, 0, mean, values, self._log_probs[:n], deterministic=True)
         blocks = ctypes.c_int32(0)
         check(self._blocks_fn(n, self.max_blocks, ctypes.byref(blocks)), "f16env_ppo_head_blocks")
-        check(self._head(self._stream(), n, mean.data_ptr(), values.data_ptr(), actions.data_ptr(),
+        check(self._head(stream_ptr(self.device), n, mean.data_ptr(), values.data_ptr(), actions.data_ptr(),
                          old_log_prob.data_ptr(), advantages.data_ptr(), returns.data_ptr(),
                          pol.blob.data_ptr() + 4 * self.logstd_off, self.hyper.data_ptr(),
                          F16_PPO_NORMALIZE_ADV if self.normalize_advantage else 0, self.max_blocks,
                          self._head_ws.data_ptr(), self._head_ws.numel(), d_mean.data_ptr(), d_values.data_ptr()),
               "f16env_ppo_loss_head")
         pol.backward_blob(observations, d_mean, d_values, out=self.grad)
-        check(self._adam(self._stream(), pol.n_floats, pol.blob.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
+        check(self._adam(stream_ptr(self.device), pol.n_floats, pol.blob.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
                          self.exp_avg_sq.data_ptr(), self.step.data_ptr(), self.hyper.data_ptr(), self.logstd_off,
                          self._head_ws.data_ptr(), blocks.value, self.stats.data_ptr()), "f16env_ppo_adam_step")
         self._bump()
@@ -149,8 +142,8 @@ class DevicePPO:
         """Clip + Adam alone on a gradient in blob layout (e.g. pol.blob.grad formed by autograd):
         f16env_ppo_adam_step without a head. `grad_blob` is not changed; stats[6:8] are written."""
         from ._lib import check
-        self.pol._check_out(grad_blob, (self.pol.n_floats,), "grad_blob", 4)
-        check(self._adam(self._stream(), self.pol.n_floats, self.pol.blob.data_ptr(), grad_blob.data_ptr(),
+        need_tensor(grad_blob, (self.pol.n_floats,), torch.float32, self.device, "grad_blob")
+        check(self._adam(stream_ptr(self.device), self.pol.n_floats, self.pol.blob.data_ptr(), grad_blob.data_ptr(),
                          self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.step.data_ptr(), self.hyper.data_ptr(),
                          0, None, 0, self.stats.data_ptr()), "f16env_ppo_adam_step")
         self._bump()

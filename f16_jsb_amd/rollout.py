@@ -25,6 +25,7 @@ from typing import Dict, Optional
 import torch
 
 from .abi import F16_FLAG_NO_AUTORESET, F16_OBS_DIM, F16_SLOT_CLIP, RolloutSlot, RolloutView
+from .buffers import need_tensor, stream_ptr
 from .layouts import as_act
 
 FIELDS = ("frames", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns")
@@ -84,8 +85,8 @@ class DeviceRolloutBuffer:
         if lv.numel() != self.n_envs or dn.numel() != self.n_envs:  # the kernel reads n_envs of each
             raise ValueError("last_values and dones must hold n_envs = %d entries, got %d and %d"
                              % (self.n_envs, lv.numel(), dn.numel()))
-        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-        check(lib().f16env_gae(ctypes.c_void_p(s), self.n_steps, self.n_envs, self.rewards.data_ptr(),
+        s = ctypes.c_void_p(stream) if stream is not None else stream_ptr(self.device)
+        check(lib().f16env_gae(s, self.n_steps, self.n_envs, self.rewards.data_ptr(),
                                self.values.data_ptr(), self.episode_starts.data_ptr(), lv.data_ptr(),
                                dn.data_ptr(), self.gamma, self.gae_lambda, self.advantages.data_ptr(),
                                self.returns.data_ptr()), "f16env_gae")
@@ -264,15 +265,13 @@ def collect_rollout(envs, buf: DeviceRolloutBuffer, seed: int = 0, step0: int = 
                                         clip=policy_fn is not None, **frame_kw)
             if defer:  # the truncated lanes' terminal observations into the stash
                 tobs = out.terminal_obs
-                check(stash_fn(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), n, buf.k, tobs.data_ptr(),
-                               tobs.stride(0), tobs.stride(1), out.terminated.data_ptr(), out.truncated.data_ptr(),
-                               t * n, stash.data_ptr(), stash_idx.data_ptr(), stash_n.data_ptr(), cap),
-                      "f16env_bootstrap_stash")
+                check(stash_fn(stream_ptr(dev), n, buf.k, tobs.data_ptr(), tobs.stride(0), tobs.stride(1),
+                               out.terminated.data_ptr(), out.truncated.data_ptr(), t * n, stash.data_ptr(),
+                               stash_idx.data_ptr(), stash_n.data_ptr(), cap), "f16env_bootstrap_stash")
             elif policy_fn is not None:  # timeout bootstrap on the step's terminal observations
                 tv = vfn(out.terminal_obs).reshape(-1).to(torch.float32).contiguous()
-                check(boot(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), n, rw0 + t * rb,
-                           out.terminated.data_ptr(), out.truncated.data_ptr(), tv.data_ptr(), buf.gamma),
-                      "f16env_bootstrap_timeouts")
+                check(boot(stream_ptr(dev), n, rw0 + t * rb, out.terminated.data_ptr(), out.truncated.data_ptr(),
+                           tv.data_ptr(), buf.gamma), "f16env_bootstrap_timeouts")
             obs = out.obs
         if defer:  # V once over every stashed terminal observation, then rewards += gamma * V
             m = int(stash_n.item())
@@ -280,8 +279,7 @@ def collect_rollout(envs, buf: DeviceRolloutBuffer, seed: int = 0, step0: int = 
                 raise RuntimeError("bootstrap stash overflow (%d > %d)" % (m, cap))
             if m:
                 tv = vfn(stash[:m]).reshape(-1).to(torch.float32).contiguous()
-                check(L.f16env_bootstrap_apply(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), m, rw0,
-                                               stash_idx.data_ptr(), tv.data_ptr(), buf.gamma),
+                check(L.f16env_bootstrap_apply(stream_ptr(dev), m, rw0, stash_idx.data_ptr(), tv.data_ptr(), buf.gamma),
                       "f16env_bootstrap_apply")
         buf.pos = T
         starts = carry
@@ -431,12 +429,7 @@ class _View:
             raise ValueError("the minibatch sampler runs on the GPU (f16env_rollout_minibatch); the rollout is on %s"
                              % fr.device)
         for f in VIEW_FIELDS:
-            x = sd[f]
-            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != fr.device \
-                    or not x.is_contiguous() or tuple(x.shape) != shapes.get(f, wrap(T, N)) \
-                    or x.data_ptr() % (16 if f == "actions" else 4):
-                raise ValueError("%s must be a contiguous float32 %s tensor on %s%s"
-                                 % (f, shapes.get(f, wrap(T, N)), fr.device, ", 16-byte aligned" if f == "actions" else ""))
+            need_tensor(sd[f], shapes.get(f, wrap(T, N)), torch.float32, fr.device, f, 16 if f == "actions" else 4)
         self.device, self.k, self.total = fr.device, k, W * T * N
         self.tensors = tuple(sd[f] for f in VIEW_FIELDS)
         self.view = RolloutView(W, k, T, N, *(x.data_ptr() for x in self.tensors))
@@ -448,11 +441,7 @@ def _check_samples(out, batch: int, k: int, device):
     if not isinstance(out, tuple) or len(out) != 6:
         raise ValueError("out must be a RolloutSamples of six tensors")
     for x, shape, name in zip(out, shapes, RolloutSamples._fields):
-        align = 16 if len(shape) > 1 else 4
-        if not isinstance(x, torch.Tensor) or x.device != device or x.dtype != torch.float32 \
-                or not x.is_contiguous() or tuple(x.shape) != shape or x.data_ptr() % align:
-            raise ValueError("out.%s must be a contiguous %d-byte aligned float32 %s tensor on %s"
-                             % (name, align, shape, device))
+        need_tensor(x, shape, torch.float32, device, "out." + name, 16 if len(shape) > 1 else 4)
 
 
 def rollout_minibatch(src, indices, k: Optional[int] = None, out: Optional[RolloutSamples] = None) -> RolloutSamples:
@@ -466,24 +455,20 @@ def rollout_minibatch(src, indices, k: Optional[int] = None, out: Optional[Rollo
     yields a row of NaN (DeviceRolloutBuffer.get range-checks its caller's indices instead).
     out: caller-owned RolloutSamples to write into. With `out` given the call allocates nothing and
     never synchronises, so it can be captured in a HIP graph."""
-    from ._lib import F16EnvError, check, lib
+    from ._lib import check, fn
 
     v = src if isinstance(src, _View) else _View(src, k)
-    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64 or indices.device != v.device \
-            or indices.dim() != 1 or not indices.is_contiguous():
-        raise ValueError("indices must be a contiguous 1-D int64 tensor on %s" % v.device)
-    batch = indices.numel()
+    batch = indices.numel() if isinstance(indices, torch.Tensor) else 0
+    need_tensor(indices, (batch,), torch.int64, v.device, "indices", 8)
     if out is None:
         e = lambda *s: torch.empty(s, dtype=torch.float32, device=v.device)  # noqa: E731
         out = RolloutSamples(e(batch, v.k, F16_OBS_DIM), e(batch, 4), e(batch), e(batch), e(batch), e(batch))
     else:
         _check_samples(out, batch, v.k, v.device)
-    fn = getattr(lib(), "f16env_rollout_minibatch", None)
-    if fn is None:
-        raise F16EnvError("this libf16env.so has no f16env_rollout_minibatch: rebuild it (python -m f16_jsb_amd.build)")
+    sampler = fn("f16env_rollout_minibatch")
     if batch:
-        check(fn(ctypes.c_void_p(torch.cuda.current_stream(v.device).cuda_stream), v.ref, batch, indices.data_ptr(),
-                 *(x.data_ptr() for x in out)), "f16env_rollout_minibatch")
+        check(sampler(stream_ptr(v.device), v.ref, batch, indices.data_ptr(), *(x.data_ptr() for x in out)),
+              "f16env_rollout_minibatch")
     return out
 
 

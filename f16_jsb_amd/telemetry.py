@@ -11,11 +11,10 @@ broken, SURVEY.md component #9.)
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from ._lib import check, lib
+from .buffers import need_tensor, stream_ptr
 
 POSE_DIM = 10
 POSE_FIELDS = ("ac_x", "ac_y", "ac_z", "q_w", "q_x", "q_y", "q_z", "goal_x", "goal_y", "goal_z")
@@ -39,9 +38,9 @@ def poses(obs: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
         raise ValueError("expected (N, K, 15) or (N, 15), got %s" % (tuple(obs.shape),))
     if out is None:
         out = torch.empty((n, POSE_DIM), dtype=torch.float32, device=obs.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-    check(lib().f16env_poses(stream, n, ctypes.c_void_p(base), stride, ctypes.c_void_p(out.data_ptr())),
-          "f16env_poses")
+    else:
+        need_tensor(out, (n, POSE_DIM), torch.float32, obs.device, "out")
+    check(lib().f16env_poses(stream_ptr(obs.device), n, base, stride, out.data_ptr()), "f16env_poses")
     return out
 
 

@@ -726,7 +726,7 @@ def test_host_checks_refuse_misshaped_buffers(torch_mod):
 
 @pytest.mark.parametrize("layout", ["contiguous", "window"])
 def test_host_checks_refuse_wrong_dtype_device_and_stride(torch_mod, layout):
-    """Every caller buffer a kernel indexes goes through F16Envs._need (device, dtype, contiguity,
+    """Every caller buffer a kernel indexes goes through buffers.need_tensor (device, dtype, contiguity,
     shape): a float16 / CPU / non-contiguous sample_actions out (both forms), a float64 rewards or
     CPU frames in rollout_random and a float16 step_rollout features are refused with ValueError
     before any launch -- one ordinary step afterwards gives the observation of a fresh handle
