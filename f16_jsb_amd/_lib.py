@@ -82,6 +82,12 @@ SIGNATURES = {
     "f16env_ppo_loss_head": (_i32, (_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _vp, _i64, _vp,
                                     _vp)),
     "f16env_ppo_adam_step": (_i32, (_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp)),
+    "f16env_ppo_dynago_workspace": (_i32, (_i64, _i32, _P(_i64))),
+    "f16env_ppo_dynago_update": (_i32, (_vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64)),
+    "f16env_ppo_loss_head_am": (_i32, (_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _vp,
+                                       _i64, _vp, _vp, _vp)),
+    "f16env_ppo_dag_step": (_i32, (_vp, _i64, _vp, _vp, _vp, _vp, _P(ctypes.c_int32), _i32, _vp, _vp, _vp, _u32, _i64,
+                                   _vp, _i32, _vp)),
     "f16env_features": (_i32, (_vp, _i64, _vp, _vp)),
     "f16env_features_strided": (_i32, (_vp, _i64, _i32, _vp, _i64, _i64, _vp)),
     "f16env_features_window_step": (_i32, (_vp, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32)),

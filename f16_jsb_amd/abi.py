@@ -198,6 +198,24 @@ PPO_HYPER = ("lr", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "beta1"
  F16_PPO_HYPER_BETA1, F16_PPO_HYPER_BETA2, F16_PPO_HYPER_EPS, F16_PPO_N_HYPER) = range(9)
 F16_PPO_N_STATS = 8
 PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm", "clip_coef")
+# AM-PPO (f16env_ppo_dynago_update, f16env_ppo_loss_head_am, f16env_ppo_dag_step): the flags and the
+# named orders of the device arrays `dynago`, `am_stats` and `dag` (include/f16env.h)
+F16_PPO_AM_NORMALIZE = 0x1      # (mod - mean(mod)) / (std(mod) + 1e-8) when n > 1
+F16_PPO_DAG_FIXED_ALPHA = 0x1   # f16env_ppo_dag_step as AlphaGrad
+PPO_DYNAGO = ("tau", "p_star", "kappa_controller", "eta", "rho", "eps", "alpha_min", "alpha_max", "rho_sat", "kappa",
+              "v_shift")
+(F16_PPO_DYNAGO_TAU, F16_PPO_DYNAGO_P_STAR, F16_PPO_DYNAGO_KAPPA_CONTROLLER, F16_PPO_DYNAGO_ETA, F16_PPO_DYNAGO_RHO,
+ F16_PPO_DYNAGO_EPS, F16_PPO_DYNAGO_ALPHA_MIN, F16_PPO_DYNAGO_ALPHA_MAX, F16_PPO_DYNAGO_RHO_SAT, F16_PPO_DYNAGO_KAPPA,
+ F16_PPO_DYNAGO_V_SHIFT, F16_PPO_N_DYNAGO) = range(12)
+F16_PPO_N_AM_STATS = 4
+PPO_AM_STATS = ("mean_raw_adv", "mean_mod_adv", "adv_norm", "alpha")
+PPO_DAG = ("tau", "p_star", "kappa", "beta", "eta", "rho", "eps", "alpha_min", "alpha_max", "k_val", "lambda_rms",
+           "s_min", "gamma", "ema_beta", "warmup_steps", "sat_every", "alpha")
+(F16_PPO_DAG_TAU, F16_PPO_DAG_P_STAR, F16_PPO_DAG_KAPPA, F16_PPO_DAG_BETA, F16_PPO_DAG_ETA, F16_PPO_DAG_RHO,
+ F16_PPO_DAG_EPS, F16_PPO_DAG_ALPHA_MIN, F16_PPO_DAG_ALPHA_MAX, F16_PPO_DAG_K_VAL, F16_PPO_DAG_LAMBDA_RMS,
+ F16_PPO_DAG_S_MIN, F16_PPO_DAG_GAMMA, F16_PPO_DAG_EMA_BETA, F16_PPO_DAG_WARMUP_STEPS, F16_PPO_DAG_SAT_EVERY,
+ F16_PPO_DAG_ALPHA, F16_PPO_N_DAG) = range(18)
+F16_PPO_DAG_MAX_SEGMENTS = 17
 POLICY_WIDTHS = (32, 64, 96, 128)
 POLICY_MAX_LAYERS = 3
 
@@ -260,3 +278,22 @@ def policy_blob_layout(d: PolicyDesc):
                 fan_in = width
     off[F16_POLICY_OFF_LOG_STD] = p
     return off, p + 4
+
+
+def policy_segments(d: PolicyDesc):
+    """f16env_ppo_dag_step's segment table for a policy's blob: [(offset, padded length, true element
+    count)] per parameter tensor in blob order -- weight and bias of every hidden layer of the pi
+    branch, then of the vf branch, the action head, the value head, log_std. The pieces tile the
+    blob: each ends where the next begins."""
+    off, total = policy_blob_layout(d)
+    pieces = []
+    for b in range(2):
+        fan_in = d.K * d.D
+        for l, width in enumerate(list(d.vf_width[:d.n_vf]) if b else list(d.pi_width[:d.n_pi])):
+            pieces += [(off[6 * b + 2 * l], width * fan_in), (off[6 * b + 2 * l + 1], width)]
+            fan_in = width
+    pieces += [(off[F16_POLICY_OFF_ACT_W], F16_ACT_DIM * d.pi_width[d.n_pi - 1]), (off[F16_POLICY_OFF_ACT_B], F16_ACT_DIM),
+               (off[F16_POLICY_OFF_VAL_W], d.vf_width[d.n_vf - 1]), (off[F16_POLICY_OFF_VAL_B], 1),
+               (off[F16_POLICY_OFF_LOG_STD], F16_ACT_DIM)]
+    ends = [o for o, _ in pieces[1:]] + [total]
+    return [(o, e - o, count) for (o, count), e in zip(pieces, ends)]

@@ -18,6 +18,9 @@
 //     element. One block, because the norm must be known before the first element moves and a blob
 //     is 26 k to 117 k floats: a second launch or a grid-wide wait would cost more than the pass.
 // No atomics, no inline assembly; the bits depend on the arguments and the data alone.
+// AM-PPO (f16_ppo_am.h, included next) shares two things defined here: the head kernel, a template
+// whose <false> instance is the standard head above and whose <true> instance takes the modulated
+// advantage of ppo_am_mod, and the step's prologue (ppo_step_prologue), which the DAG step repeats.
 #pragma once
 
 namespace f16 {
@@ -36,6 +39,9 @@ struct PpoHeadArgs {
   double* ws;
   int64_t n;
   int32_t normalize;
+  // the AM instance alone (f16_ppo_am.h): target_values holds old_values, ws[0], ws[1], ws[3] the
+  // modulated advantages' mean, std and the minibatch's norm
+  const float* dynago; const float* am_state;
 };
 
 // red[t] over t = 0 .. T-1 -> red[0], halving tree (T a power of two); every thread of the block calls it
@@ -72,6 +78,34 @@ __global__ __launch_bounds__(PPO_WIDE) void f16_ppo_adv_stats_kernel(const float
   }
 }
 
+// AM-PPO's modulated advantage (ppo.py:87-97 with update_ema = False), the one place it is formed:
+// the AM head's statistics launch (f16_ppo_am.h) and its rows both call ppo_am_mod.
+//   mod = |A| (kappa tanh(alpha A / (N + eps)) + v_shift), fp64 from the float32 inputs, alpha the
+//   controller's state[0] as stored, N the minibatch's norm; n <= 1: mod = A (ppo.py:40-41)
+struct PpoAmCoef {
+  double alpha, den, kappa, v_shift;
+  int32_t identity;
+};
+
+__device__ __forceinline__ PpoAmCoef ppo_am_coef(const float* dynago, const float* state, const double norm,
+                                                 const int64_t n) {
+  PpoAmCoef c;
+  c.alpha = (double)state[0];
+  c.den = norm + (double)dynago[F16_PPO_DYNAGO_EPS];
+  c.kappa = (double)dynago[F16_PPO_DYNAGO_KAPPA];
+  c.v_shift = (double)dynago[F16_PPO_DYNAGO_V_SHIFT];
+  c.identity = n <= 1;
+  return c;
+}
+
+__device__ __forceinline__ double ppo_am_mod(const float A, const PpoAmCoef& c) {
+  const double a = (double)A;
+  return c.identity ? a : fabs(a) * (c.kappa * tanh(c.alpha * a / c.den) + c.v_shift);
+}
+
+// AM = false: standard PPO's head. AM = true: f16env_ppo_loss_head_am's, the advantage and the value
+// target from ppo_am_mod; every line outside the two `if constexpr` is shared
+template <bool AM>
 __global__ __launch_bounds__(PPO_HEAD_THREADS) void f16_ppo_head_kernel(const PpoHeadArgs a) {
   __shared__ double red[PPO_HEAD_THREADS];
   const int t = (int)threadIdx.x;
@@ -101,6 +135,8 @@ __global__ __launch_bounds__(PPO_HEAD_THREADS) void f16_ppo_head_kernel(const Pp
   double acc[PPO_SUMS];
 #pragma unroll
   for (int k = 0; k < PPO_SUMS; ++k) acc[k] = 0.0;
+  PpoAmCoef am{};
+  if constexpr (AM) am = ppo_am_coef(a.dynago, a.am_state, a.ws[3], a.n);
   const int64_t stride = (int64_t)gridDim.x * PPO_HEAD_THREADS;
   for (int64_t row = (int64_t)blockIdx.x * PPO_HEAD_THREADS + t; row < a.n; row += stride) {
     const float4 m4 = reinterpret_cast<const float4*>(a.mean)[row];
@@ -117,7 +153,14 @@ __global__ __launch_bounds__(PPO_HEAD_THREADS) void f16_ppo_head_kernel(const Pp
     const double log_r = lp - (double)a.old_log_prob[row];
     const double r64 = exp(log_r);
     const float r = (float)r64;
-    const float A = a.normalize ? (float)(((double)a.advantages[row] - a_mean) / a_den) : a.advantages[row];
+    float A;
+    double mod = 0.0;
+    if constexpr (AM) {
+      mod = ppo_am_mod(a.advantages[row], am);
+      A = a.normalize ? (float)((mod - a_mean) / a_den) : (float)mod;
+    } else {
+      A = a.normalize ? (float)(((double)a.advantages[row] - a_mean) / a_den) : a.advantages[row];
+    }
     // torch.min over (s1, s2) with torch.clamp under autograd: the clamp passes the gradient on
     // [lo, hi] inclusive; outside it only the unclipped arm carries one, and only where it is the smaller
     const double s1 = (double)A * r64, s2 = (double)A * fmin(fmax(r64, lo), hi);
@@ -131,7 +174,9 @@ __global__ __launch_bounds__(PPO_HEAD_THREADS) void f16_ppo_head_kernel(const Pp
       acc[j] += (double)g * ((double)z * (double)z - 1.0);
     }
     reinterpret_cast<float4*>(a.d_mean)[row] = make_float4(dm[0], dm[1], dm[2], dm[3]);
-    const float dv = a.values[row] - a.target_values[row];
+    float dv;
+    if constexpr (AM) dv = (float)((double)a.values[row] - (mod + (double)a.target_values[row]));
+    else dv = a.values[row] - a.target_values[row];
     a.d_values[row] = (vf_coef * 2.0f * inv_n) * dv;
     acc[4] += -fmin(s1, s2);
     acc[5] += (double)dv * (double)dv;
@@ -145,7 +190,7 @@ __global__ __launch_bounds__(PPO_HEAD_THREADS) void f16_ppo_head_kernel(const Pp
   }
   if (blockIdx.x == 0 && t == 0) {
     a.ws[2] = (double)a.n;
-    a.ws[3] = 0.0;
+    if constexpr (!AM) a.ws[3] = 0.0;
   }
 }
 
@@ -159,56 +204,71 @@ struct PpoStepArgs {
   int32_t head_blocks;
 };
 
+// What every optimiser step does ahead of its own arithmetic (f16_ppo_adam_kernel, f16_ppo_dag_kernel
+// of f16_ppo_am.h), by every thread of the one block: with a head workspace the head's partials in
+// block order, d_log_std into grad (and dls) and stats[0..5]; always the gradient's norm and the
+// clip factor, stats[6..7]. Returns the clip factor; ends on a barrier.
+__device__ __forceinline__ double ppo_step_prologue(double* red, double* sums, float* dls, const int t, const float* blob,
+                                                    float* grad, const float* hyper, const double* head_ws,
+                                                    const int32_t head_blocks, float* stats, const int64_t nf,
+                                                    const int64_t logstd) {
+  const float ent_coef = hyper[2], vf_coef = hyper[3], max_norm = hyper[4];
+  const bool head = head_ws != nullptr;
+  if (head) {
+    if (t < PPO_SUMS) {
+      double s = 0.0;
+      for (int b = 0; b < head_blocks; ++b) s += head_ws[PPO_HEADER + (int64_t)b * PPO_SUMS + t];
+      sums[t] = s;
+    }
+    __syncthreads();
+    if (t < 4) {
+      dls[t] = (float)(sums[t] - (double)ent_coef);
+      grad[logstd + t] = dls[t];
+    }
+    __syncthreads();
+  }
+  double q = 0.0;
+  for (int64_t i = t; i < nf; i += PPO_WIDE) {
+    // (the four slots just written are read from LDS, not back from memory)
+    const float g = (head && i >= logstd && i < logstd + 4) ? dls[i - logstd] : grad[i];
+    q += (double)g * (double)g;
+  }
+  const double total_norm = sqrt(ppo_block_sum<PPO_WIDE>(red, t, q));
+  const double coef = fmin(1.0, (double)max_norm / (total_norm + 1e-6));
+  if (t == 0 && stats) {
+    if (head) {
+      const double n = head_ws[2];
+      double ent = 0.0;
+      for (int j = 0; j < 4; ++j) ent += 0.5 + 0.918938533204672742 + (double)blob[logstd + j];
+      const double pl = sums[4] / n, vl = sums[5] / n;
+      stats[0] = (float)pl;
+      stats[1] = (float)vl;
+      stats[2] = (float)-ent;
+      stats[3] = (float)(pl + (double)ent_coef * -ent + (double)vf_coef * vl);
+      stats[4] = (float)(sums[6] / n);
+      stats[5] = (float)(sums[7] / n);
+    }
+    stats[6] = (float)total_norm;
+    stats[7] = (float)coef;
+  }
+  __syncthreads();  // (the statistics read log_std ahead of its update)
+  return coef;
+}
+
 __global__ __launch_bounds__(PPO_WIDE) void f16_ppo_adam_kernel(const PpoStepArgs a) {
   __shared__ double red[PPO_WIDE];
   __shared__ double sums[PPO_SUMS];
   __shared__ float dls[4];
   const int t = (int)threadIdx.x;
   const int32_t step_next = *a.step + 1;  // (stored back by thread 0 after the block's barriers)
-  const float lr = a.hyper[0], ent_coef = a.hyper[2], vf_coef = a.hyper[3], max_norm = a.hyper[4];
+  const float lr = a.hyper[0];
   const float beta1 = a.hyper[5], beta2 = a.hyper[6], eps = a.hyper[7];
   const bool head = a.head_ws != nullptr;
-  if (head) {
-    if (t < PPO_SUMS) {
-      double s = 0.0;
-      for (int b = 0; b < a.head_blocks; ++b) s += a.head_ws[PPO_HEADER + (int64_t)b * PPO_SUMS + t];
-      sums[t] = s;
-    }
-    __syncthreads();
-    if (t < 4) {
-      dls[t] = (float)(sums[t] - (double)ent_coef);
-      a.grad[a.logstd + t] = dls[t];
-    }
-    __syncthreads();
-  }
-  // (the four slots just written are read from LDS, not back from memory)
+  const double coef = ppo_step_prologue(red, sums, dls, t, a.blob, a.grad, a.hyper, a.head_ws, a.head_blocks, a.stats,
+                                        a.nf, a.logstd);
   auto g_at = [&](const int64_t i) -> float {
     return (head && i >= a.logstd && i < a.logstd + 4) ? dls[i - a.logstd] : a.grad[i];
   };
-  double q = 0.0;
-  for (int64_t i = t; i < a.nf; i += PPO_WIDE) {
-    const float g = g_at(i);
-    q += (double)g * (double)g;
-  }
-  const double total_norm = sqrt(ppo_block_sum<PPO_WIDE>(red, t, q));
-  const double coef = fmin(1.0, (double)max_norm / (total_norm + 1e-6));
-  if (t == 0 && a.stats) {
-    if (head) {
-      const double n = a.head_ws[2];
-      double ent = 0.0;
-      for (int j = 0; j < 4; ++j) ent += 0.5 + 0.918938533204672742 + (double)a.blob[a.logstd + j];
-      const double pl = sums[4] / n, vl = sums[5] / n;
-      a.stats[0] = (float)pl;
-      a.stats[1] = (float)vl;
-      a.stats[2] = (float)-ent;
-      a.stats[3] = (float)(pl + (double)ent_coef * -ent + (double)vf_coef * vl);
-      a.stats[4] = (float)(sums[6] / n);
-      a.stats[5] = (float)(sums[7] / n);
-    }
-    a.stats[6] = (float)total_norm;
-    a.stats[7] = (float)coef;
-  }
-  __syncthreads();  // (the statistics read log_std ahead of its update)
   // torch.optim.Adam's single-tensor step on float32 state, each element's arithmetic in fp64 and
   // rounded once per stored value: a clip factor rounded to float32 would put one common relative
   // error on every element of a step, twice over in the second moment
@@ -281,7 +341,7 @@ static int ppo_loss_head_impl(void* stream, int64_t n, const float* mean, const 
   a.normalize = ((flags & F16_PPO_NORMALIZE_ADV) && n > 1) ? 1 : 0;
   if (a.normalize)
     hipLaunchKernelGGL(f16_ppo_adv_stats_kernel, dim3(1), dim3(PPO_WIDE), 0, (hipStream_t)stream, advantages, n, a.ws);
-  hipLaunchKernelGGL(f16_ppo_head_kernel, dim3((unsigned)grid), dim3(PPO_HEAD_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(f16_ppo_head_kernel<false>, dim3((unsigned)grid), dim3(PPO_HEAD_THREADS), 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return 0;
 }

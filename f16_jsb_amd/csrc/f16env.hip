@@ -2565,6 +2565,7 @@ static EnvArgs env_args(const f16env* h) {
 
 #include "f16_policy.h"
 #include "f16_ppo.h"
+#include "f16_ppo_am.h"
 
 extern "C" {
 
@@ -3686,6 +3687,32 @@ int f16env_ppo_adam_step(void* stream, int64_t n_floats, float* blob, float* gra
                          const void* head_workspace, int32_t head_blocks, float* stats) {
   return ppo_adam_step_impl(stream, n_floats, blob, grad_blob, exp_avg, exp_avg_sq, step, hyper, log_std_offset,
                             head_workspace, head_blocks, stats);
+}
+
+int f16env_ppo_dynago_workspace(int64_t n, int32_t max_blocks, int64_t* bytes_out) {
+  return ppo_dynago_workspace_impl(n, max_blocks, bytes_out);
+}
+
+int f16env_ppo_dynago_update(void* stream, int64_t n, const float* advantages, const float* dynago, float* state,
+                             int32_t max_blocks, void* workspace, int64_t workspace_bytes) {
+  return ppo_dynago_update_impl(stream, n, advantages, dynago, state, max_blocks, workspace, workspace_bytes);
+}
+
+int f16env_ppo_loss_head_am(void* stream, int64_t n, const float* mean, const float* values, const float* actions,
+                            const float* old_log_prob, const float* advantages, const float* old_values,
+                            const float* log_std, const float* hyper, const float* dynago, const float* state,
+                            uint32_t flags, int32_t max_blocks, void* workspace, int64_t workspace_bytes, float* d_mean,
+                            float* d_values, float* am_stats) {
+  return ppo_loss_head_am_impl(stream, n, mean, values, actions, old_log_prob, advantages, old_values, log_std, hyper,
+                               dynago, state, flags, max_blocks, workspace, workspace_bytes, d_mean, d_values, am_stats);
+}
+
+int f16env_ppo_dag_step(void* stream, int64_t n_floats, float* blob, float* grad_blob, const float* hyper,
+                        const float* dag, const int32_t* segments, int32_t n_segments, float* seg_state,
+                        double* dag_state, int32_t* dag_counters, uint32_t flags, int64_t log_std_offset,
+                        const void* head_workspace, int32_t head_blocks, float* stats) {
+  return ppo_dag_step_impl(stream, n_floats, blob, grad_blob, hyper, dag, segments, n_segments, seg_state, dag_state,
+                           dag_counters, flags, log_std_offset, head_workspace, head_blocks, stats);
 }
 
 int f16env_features(void* stream, int64_t n_frames, const float* obs, float* feat) {

@@ -39,6 +39,9 @@
  *   f16env_ppo_loss_head <- ppo.py:355-388 (the clipped surrogate, value and entropy losses, the
  *                      statistics) and autograd through them down to (mean, values, log_std)
  *   f16env_ppo_adam_step <- ppo.py:392-395 clip_grad_norm_ and torch.optim.Adam.step, on the blob
+ *   f16env_ppo_dynago_update <- ppo.py:289-306, dynago_transform_advantages (:29-99) over the rollout
+ *   f16env_ppo_loss_head_am <- ppo.py:327-388 with use_am_ppo (modulated advantages and value target)
+ *   f16env_ppo_dag_step <- ppo.py:399-400 with ppo/optim/sgd.py's DAG.step (:219-344) or AlphaGrad.step
  *   f16env_features <- jsbsim_gym/features.py:37-67 JSBSimFeatureExtractor.forward (8f rank 3)
  *   f16env_features_window_step <- the same per step on a windowed observation, one frame each
  *   f16env_poses    <- jsbsim_gym.py:381-415 JSBSimEnv.render state -> Viewer poses (8f rank 4)
@@ -73,7 +76,10 @@ extern "C" {
  * policy's mean and value in the blob's layout), bound the same way.
  * Still 7: new f16env_ppo_workspace, f16env_ppo_head_blocks, f16env_ppo_loss_head and
  * f16env_ppo_adam_step (the PPO update between the forward and the new weights), bound the same
- * way. */
+ * way.
+ * Still 7: new f16env_ppo_dynago_workspace, f16env_ppo_dynago_update, f16env_ppo_loss_head_am and
+ * f16env_ppo_dag_step (AM-PPO: the DynAGO controller, its loss head and the DAG / AlphaGrad step),
+ * bound the same way. */
 #define F16ENV_ABI_VERSION 7
 
 /* Frame layout (jsbsim_gym.py:12-25 STATE_FORMAT + goal, :172-197) */
@@ -701,6 +707,122 @@ int f16env_ppo_loss_head(void* stream, int64_t n, const float* mean, const float
 int f16env_ppo_adam_step(void* stream, int64_t n_floats, float* blob, float* grad_blob, float* exp_avg,
                          float* exp_avg_sq, int32_t* step, const float* hyper, int64_t log_std_offset,
                          const void* head_workspace, int32_t head_blocks, float* stats);
+
+/* AM-PPO on the device (still ABI 7: four symbols added), the reference's training recipe
+ * (train.py: use_am_ppo, dynago_*, am_ppo_optimizer): the DynAGO controller, the loss head on
+ * modulated advantages, and the DAG / AlphaGrad optimiser step. All of them: no handle;
+ * stream-ordered; no sync and no allocation; safe under stream capture; no atomics, every sum in
+ * fp64 and in a fixed order, the bits depend on the arguments and the data alone. A bad argument (a
+ * NULL or misaligned pointer, negative n, max_blocks < 0, unknown flags, a workspace smaller than
+ * stated, a bad segment table) returns < 0 with f16env_last_error set, before any launch.
+ *
+ * dynago: a DEVICE array of F16_PPO_N_DYNAGO floats the kernels read when they run,
+ *   [F16_PPO_DYNAGO_TAU, _P_STAR, _KAPPA_CONTROLLER, _ETA, _RHO, _EPS, _ALPHA_MIN, _ALPHA_MAX, _RHO_SAT,
+ *    _KAPPA, _V_SHIFT];  state: a DEVICE float[2], (alpha, sat) = ppo.py's alpha_A_ema_state and
+ *   prev_saturation_A_ema_state.
+ *
+ * f16env_ppo_dynago_update: stable_baselines3/ppo/ppo.py:289-306, the call of
+ * dynago_transform_advantages (:29-99) with update_ema = True over the whole rollout's advantages
+ * (n float32, 16-B aligned; the flattened (T, N) buffer). For n > 1, every scalar in fp64:
+ *   N = sqrt(sum A^2); sigma = std_unbiased(A) + eps (from the fp64 sums of A and A^2)
+ *   a_hat = kappa_controller (N + eps) / (sigma + eps) (p_star / (sat + eps))^eta   (eps twice, :61, :71)
+ *   alpha' = clamp((1 - rho) alpha + rho a_hat, alpha_min, alpha_max), rounded to float32 -> state[0]
+ *   sat' = (1 - rho_sat) sat + rho_sat mean(|A| (alpha' / (N + eps)) > tau) -> state[1], alpha' as stored
+ * n <= 1 launches nothing and leaves the state as it is (:40-41). Three launches; the array is read
+ * twice, as float4, by grid = min(ceil(ceil(n / 4) / 256), max_blocks or 2048) blocks of 256
+ * threads; the blocks' partial sums lie in the workspace and are added in a fixed order by the next
+ * launch.
+ *   workspace   caller-owned device memory, 8-B aligned, at least f16env_ppo_dynago_workspace(n,
+ *               max_blocks) bytes (a pure host function, no device; monotone in both; 0 for n <= 1)
+ *
+ * f16env_ppo_loss_head_am: f16env_ppo_loss_head for ppo.py:327-352, :368-372 (use_am_ppo). The same
+ * contract with old_values (n) where target_values was, dynago and state read and not written (the
+ * EMAs are frozen inside the epochs, :338), flags F16_PPO_AM_NORMALIZE (:349-350) or 0, and am_stats, a
+ * device float[4] or NULL: mean(A), mean(mod), N_mb, the alpha used (:329, :340 log the first two).
+ * A one-block launch ahead of the rows forms N_mb = ||A||_2 over the minibatch, then the mean and
+ * the unbiased std of mod; per row, in fp64 from the float32 inputs:
+ *   mod = |A| (kappa tanh(alpha A / (N_mb + eps)) + v_shift); n <= 1: mod = A
+ *   A^ = (mod - mean(mod)) / (std(mod) + 1e-8) with the flag and n > 1, else mod, rounded to float32
+ *   target = mod + old_values (the mod that is not normalised, :369)
+ * mod is a constant to autograd: d_mean, d_values and the eight sums are f16env_ppo_loss_head's with
+ * A^ and target in place. The workspace is f16env_ppo_workspace's and is what f16env_ppo_adam_step
+ * and f16env_ppo_dag_step take as head_workspace.
+ *
+ * f16env_ppo_dag_step: ppo.py:399-400 with the optimiser PPO._setup_model builds as DAG(params, lr)
+ * (ppo/optim/sgd.py:219-344: no momentum, weight decay, nesterov, maximize, k_sched, exact sigma),
+ * in place on the blob, ONE block of 1024 threads. First f16env_ppo_adam_step's prologue, word for
+ * word (head_workspace, head_blocks, log_std_offset, stats[0..7]); the optimiser sees g coef.
+ *   dag        a DEVICE array of F16_PPO_N_DAG floats, [F16_PPO_DAG_TAU, _P_STAR, _KAPPA, _BETA, _ETA,
+ *              _RHO, _EPS, _ALPHA_MIN, _ALPHA_MAX, _K_VAL, _LAMBDA_RMS, _S_MIN, _GAMMA, _EMA_BETA,
+ *              _WARMUP_STEPS, _SAT_EVERY, _ALPHA]; lr and max_grad_norm come from hyper
+ *   segments   a HOST array of n_segments x 3 int32, read during the call (it travels in the
+ *              kernel's arguments): per parameter tensor its offset into the blob, its padded
+ *              length and its true element count d_s; 1 .. 17 segments, ascending, no overlap.
+ *              Pads carry gradient +0 and weight +0 and come out all-bits zero (tanh(0) = 0).
+ *   seg_state  device float[2 n_segments]: (alpha_s, sat_s) per tensor (sgd.py:170-171: 1, 0)
+ *   dag_state  device double[4]: s_t (1 at the start), rms_t_ema, rms0_ema, 0
+ *   dag_counters device int32[4]: global_step, rms_t_ema is set, rms0_ema is set, 0 ("unset" is a
+ *              flag here, None in sgd.py:160-161)
+ * Per tensor s, d_total = sum d_s, in fp64:
+ *   n_s = ||coef g_s||_2; sigma_s = n_s / sqrt(d_s)
+ *   a_hat = kappa (n_s + eps) / (sigma_s + eps) (d_s / d_total)^beta (p_star / (sat_s + eps))^eta s_t
+ *   alpha_s = clamp((1 - rho) alpha_s + rho a_hat, alpha_min, alpha_max), stored float32, used as stored
+ *   x = (alpha_s / s_t) coef g / (n_s + eps); u = k_val s_t tanh(x); blob <- blob - lr u (rounded once)
+ *   sat_s = (count of |x| > tau) / d_s, only when global_step % sat_every == 0
+ * then sgd.py:326-343 with s_t as it was on entry throughout the step: rms_now = sqrt(sum u^2 /
+ * d_total); rms_t_ema = rms_now if unset else ema_beta rms_t_ema + (1 - ema_beta) rms_now; while
+ * global_step < warmup_steps rms0_ema follows rms_t_ema the same way, afterwards s_t = s_min +
+ * (1 - s_min) clamp(rms_t_ema / (lambda_rms rms0_ema), 0, 1)^gamma; global_step += 1.
+ * F16_PPO_DAG_FIXED_ALPHA makes the same kernel AlphaGrad (sgd.py:471-498 with its defaults): the one
+ * alpha = dag[F16_PPO_DAG_ALPHA] for every tensor, k_val = s_t = 1, eps = dag[F16_PPO_DAG_EPS]
+ * (AlphaGrad's epsilon); seg_state, dag_state and dag_counters are neither read nor written.
+ * grad_blob is not scaled. n_floats == 0 launches nothing. */
+#define F16_PPO_AM_NORMALIZE 0x1
+#define F16_PPO_DAG_FIXED_ALPHA 0x1
+#define F16_PPO_DYNAGO_TAU 0
+#define F16_PPO_DYNAGO_P_STAR 1
+#define F16_PPO_DYNAGO_KAPPA_CONTROLLER 2
+#define F16_PPO_DYNAGO_ETA 3
+#define F16_PPO_DYNAGO_RHO 4
+#define F16_PPO_DYNAGO_EPS 5
+#define F16_PPO_DYNAGO_ALPHA_MIN 6
+#define F16_PPO_DYNAGO_ALPHA_MAX 7
+#define F16_PPO_DYNAGO_RHO_SAT 8
+#define F16_PPO_DYNAGO_KAPPA 9
+#define F16_PPO_DYNAGO_V_SHIFT 10
+#define F16_PPO_N_DYNAGO 11
+#define F16_PPO_N_AM_STATS 4
+#define F16_PPO_DAG_TAU 0
+#define F16_PPO_DAG_P_STAR 1
+#define F16_PPO_DAG_KAPPA 2
+#define F16_PPO_DAG_BETA 3
+#define F16_PPO_DAG_ETA 4
+#define F16_PPO_DAG_RHO 5
+#define F16_PPO_DAG_EPS 6
+#define F16_PPO_DAG_ALPHA_MIN 7
+#define F16_PPO_DAG_ALPHA_MAX 8
+#define F16_PPO_DAG_K_VAL 9
+#define F16_PPO_DAG_LAMBDA_RMS 10
+#define F16_PPO_DAG_S_MIN 11
+#define F16_PPO_DAG_GAMMA 12
+#define F16_PPO_DAG_EMA_BETA 13
+#define F16_PPO_DAG_WARMUP_STEPS 14
+#define F16_PPO_DAG_SAT_EVERY 15
+#define F16_PPO_DAG_ALPHA 16
+#define F16_PPO_N_DAG 17
+#define F16_PPO_DAG_MAX_SEGMENTS 17
+int f16env_ppo_dynago_workspace(int64_t n, int32_t max_blocks, int64_t* bytes_out);
+int f16env_ppo_dynago_update(void* stream, int64_t n, const float* advantages, const float* dynago, float* state,
+                             int32_t max_blocks, void* workspace, int64_t workspace_bytes);
+int f16env_ppo_loss_head_am(void* stream, int64_t n, const float* mean, const float* values, const float* actions,
+                            const float* old_log_prob, const float* advantages, const float* old_values,
+                            const float* log_std, const float* hyper, const float* dynago, const float* state,
+                            uint32_t flags, int32_t max_blocks, void* workspace, int64_t workspace_bytes, float* d_mean,
+                            float* d_values, float* am_stats);
+int f16env_ppo_dag_step(void* stream, int64_t n_floats, float* blob, float* grad_blob, const float* hyper,
+                        const float* dag, const int32_t* segments, int32_t n_segments, float* seg_state,
+                        double* dag_state, int32_t* dag_counters, uint32_t flags, int64_t log_std_offset,
+                        const void* head_workspace, int32_t head_blocks, float* stats);
 
 /* Policy features of every observation frame, replacing
  * jsbsim_gym/features.py:37-67 JSBSimFeatureExtractor.forward (float32):
