@@ -234,6 +234,35 @@ class PolicyDesc(ctypes.Structure):
     ]
 
 
+# the LMA features extractor in front of the MLPs (f16env_policy_lma_forward): blob slots past the MLP's
+F16_LMA_N_OFFSETS = 58
+F16_LMA_OFF_PE, F16_LMA_OFF_WE_W, F16_LMA_OFF_WE_B, F16_LMA_OFF_W2_W, F16_LMA_OFF_W2_B = 17, 18, 19, 20, 21
+F16_LMA_OFF_BLOCK0 = 22   # block i's slots start at F16_LMA_OFF_BLOCK0 + F16_LMA_BLOCK_SLOTS * i
+F16_LMA_BLOCK_SLOTS = 12
+(F16_LMA_BLK_LN1_W, F16_LMA_BLK_LN1_B, F16_LMA_BLK_ATTN_W, F16_LMA_BLK_ATTN_B, F16_LMA_BLK_PROJ_W, F16_LMA_BLK_PROJ_B,
+ F16_LMA_BLK_LN2_W, F16_LMA_BLK_LN2_B, F16_LMA_BLK_FC_W, F16_LMA_BLK_FC_B, F16_LMA_BLK_PROJ2_W,
+ F16_LMA_BLK_PROJ2_B) = range(12)
+LMA_EMBED_DIM, LMA_D_NEW, LMA_HEADS_LATENT, LMA_FEATURES, LMA_MAX_LAYERS, LMA_MAX_L_NEW = 64, 32, 4, 17, 3, 5
+
+
+class LmaDesc(ctypes.Structure):
+    """f16_lma_desc (include/f16env.h): the shape of the LMA features extractor; sixteen int32,
+    passed to the library by address."""
+    _fields_ = [
+        ("K", ctypes.c_int32),
+        ("D", ctypes.c_int32),
+        ("embed_dim", ctypes.c_int32),
+        ("heads_stacking", ctypes.c_int32),
+        ("L_new", ctypes.c_int32),
+        ("C_new", ctypes.c_int32),
+        ("d_new", ctypes.c_int32),
+        ("heads_latent", ctypes.c_int32),
+        ("ff_hidden", ctypes.c_int32),
+        ("n_layers", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 6),
+    ]
+
+
 # the header's struct names and their mirrors (tests/test_abi_cpu.py holds every field's offset and size together)
 STRUCTS = {"f16env_config": EnvConfig, "f16env_rollout_slot": RolloutSlot, "F16RolloutView": RolloutView,
            "f16_policy_desc": PolicyDesc}
@@ -259,13 +288,14 @@ def policy_desc(stack_k: int, frame_dim: int, pi_widths, vf_widths, activation="
     return d
 
 
-def policy_blob_layout(d: PolicyDesc):
-    """Python twin of f16env_policy_blob_layout: (offsets[F16_POLICY_N_OFFSETS], n_floats)."""
+def policy_blob_layout(d: PolicyDesc, fan_in0=None):
+    """Python twin of f16env_policy_blob_layout: (offsets[F16_POLICY_N_OFFSETS], n_floats).
+    fan_in0: the first layers' fan-in when it is not K D (the LMA extractor's features)."""
     off = [-1] * F16_POLICY_N_OFFSETS
     p = 0
     for heads in (False, True):  # the hidden layers of both branches, then the two heads (one tile each)
         for b in range(2):
-            fan_in = d.K * d.D
+            fan_in = d.K * d.D if fan_in0 is None else int(fan_in0)
             widths = list(d.vf_width[:d.n_vf]) if b else list(d.pi_width[:d.n_pi])
             for l, width in enumerate(widths + [32]):
                 head = l == len(widths)
@@ -297,3 +327,77 @@ def policy_segments(d: PolicyDesc):
                (off[F16_POLICY_OFF_LOG_STD], F16_ACT_DIM)]
     ends = [o for o, _ in pieces[1:]] + [total]
     return [(o, e - o, count) for (o, count), e in zip(pieces, ends)]
+
+
+def lma_new_dims(stack_k: int, embed_dim: int = LMA_EMBED_DIM):
+    """(L_new, C_new) of the extractor's re-chunk: L_new is the divisor of K embed_dim closest to
+    max(K // 2, 1); at a distance delta the candidate below the target is tried before the one
+    above (so K = 7, target 3, takes 2, not 4). C_new = K embed_dim / L_new."""
+    total, target = int(stack_k) * int(embed_dim), max(int(stack_k) // 2, 1)
+    if total < 1:
+        raise ValueError("stack_k and embed_dim must be positive")
+    for delta in range(total + 1):
+        for cand in (target - delta, target + delta):
+            if cand > 0 and total % cand == 0:
+                return cand, total // cand
+    raise AssertionError("unreachable: 1 divides everything")
+
+
+def lma_desc(stack_k: int, frame_dim: int, embed_dim: int = LMA_EMBED_DIM, heads_stacking: int = 4,
+             d_new: int = LMA_D_NEW, heads_latent: int = LMA_HEADS_LATENT, ff_hidden: int = 128,
+             n_layers: int = 2) -> LmaDesc:
+    """The descriptor of the reference's extractor at a stack length; every field outside the
+    kernel's family is refused by name."""
+    k, d, hs = int(stack_k), int(frame_dim), int(heads_stacking)
+    if not 1 <= k <= 10:
+        raise ValueError("stack_k must be in 1..10, got %d" % k)
+    if d not in (15, 17):
+        raise ValueError("frame_dim must be 15 or 17, got %d" % d)
+    if int(embed_dim) != LMA_EMBED_DIM:
+        raise ValueError("embed_dim must be %d, got %d" % (LMA_EMBED_DIM, embed_dim))
+    if hs < 1 or LMA_EMBED_DIM % hs or (LMA_EMBED_DIM // hs) % 2:
+        raise ValueError("heads_stacking must divide embed_dim into an even dk, got %d" % hs)
+    if int(d_new) != LMA_D_NEW:
+        raise ValueError("d_new must be %d, got %d" % (LMA_D_NEW, d_new))
+    if int(heads_latent) != LMA_HEADS_LATENT:
+        raise ValueError("heads_latent must be %d, got %d" % (LMA_HEADS_LATENT, heads_latent))
+    if int(ff_hidden) not in POLICY_WIDTHS:
+        raise ValueError("ff_hidden must be 32, 64, 96 or 128, got %d" % ff_hidden)
+    if not 0 <= int(n_layers) <= LMA_MAX_LAYERS:
+        raise ValueError("n_layers must be in 0..%d, got %d" % (LMA_MAX_LAYERS, n_layers))
+    m = LmaDesc()
+    m.K, m.D, m.embed_dim, m.heads_stacking = k, d, LMA_EMBED_DIM, hs
+    m.L_new, m.C_new = lma_new_dims(k, LMA_EMBED_DIM)
+    m.d_new, m.heads_latent, m.ff_hidden, m.n_layers = LMA_D_NEW, LMA_HEADS_LATENT, int(ff_hidden), int(n_layers)
+    return m
+
+
+def lma_blob_layout(d: PolicyDesc, m: LmaDesc):
+    """Python twin of f16env_policy_lma_blob_layout: (offsets[F16_LMA_N_OFFSETS], n_floats)."""
+    if (m.K, m.D) != (d.K, d.D):
+        raise ValueError("the LMA descriptor's K and D must equal the policy descriptor's")
+    if m.L_new * m.C_new != m.K * m.embed_dim:
+        raise ValueError("L_new * C_new must equal K * embed_dim")
+    off, p = policy_blob_layout(d, m.L_new * m.d_new)
+    off = off + [-1] * (F16_LMA_N_OFFSETS - F16_POLICY_N_OFFSETS)
+
+    def put(slot, floats):
+        nonlocal p
+        off[slot] = p
+        p += floats
+    nks_d = m.d_new // 2
+    put(F16_LMA_OFF_PE, m.K * m.embed_dim)
+    put(F16_LMA_OFF_WE_W, (m.embed_dim // 32) * ((LMA_FEATURES + 1) // 2) * 64)
+    put(F16_LMA_OFF_WE_B, m.embed_dim)
+    put(F16_LMA_OFF_W2_W, (m.C_new // 2) * 64)
+    put(F16_LMA_OFF_W2_B, m.d_new)
+    for i in range(m.n_layers):
+        s = F16_LMA_OFF_BLOCK0 + F16_LMA_BLOCK_SLOTS * i
+        for slot, floats in ((F16_LMA_BLK_LN1_W, m.d_new), (F16_LMA_BLK_LN1_B, m.d_new),
+                             (F16_LMA_BLK_ATTN_W, 3 * nks_d * 64), (F16_LMA_BLK_ATTN_B, 3 * m.d_new),
+                             (F16_LMA_BLK_PROJ_W, nks_d * 64), (F16_LMA_BLK_PROJ_B, m.d_new),
+                             (F16_LMA_BLK_LN2_W, m.d_new), (F16_LMA_BLK_LN2_B, m.d_new),
+                             (F16_LMA_BLK_FC_W, (m.ff_hidden // 32) * nks_d * 64), (F16_LMA_BLK_FC_B, m.ff_hidden),
+                             (F16_LMA_BLK_PROJ2_W, (m.ff_hidden // 2) * 64), (F16_LMA_BLK_PROJ2_B, m.d_new)):
+            put(s + slot, floats)
+    return off, p

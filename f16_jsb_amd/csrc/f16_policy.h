@@ -544,13 +544,14 @@ static const char* policy_desc_error(const f16_policy_desc* d) {
 // The blob: per branch (pi, then vf) each hidden layer's weight as [tiles of 32 outputs][k-steps][2][32]
 // (element = W[32 to + i][2 s + h], inputs past the layer's fan-in zero) then its bias; then the
 // action head and the value head in the same form as one tile each (outputs past 4 / 1 zero, a bias of
-// 32); then log_std[4]. Every piece starts on a multiple of 4 floats.
-static int64_t policy_layout(const f16_policy_desc* d, int64_t* off, PolicyOp* ops) {
+// 32); then log_std[4]. Every piece starts on a multiple of 4 floats. fan_in0: the first layers'
+// fan-in when it is not K D (the LMA extractor's features, f16_policy_lma.h).
+static int64_t policy_layout(const f16_policy_desc* d, int64_t* off, PolicyOp* ops, const int fan_in0 = 0) {
   int64_t p = 0;
   for (int i = 0; i < F16_POLICY_N_OFFSETS; ++i) off[i] = -1;
   for (int pass = 0; pass < 2; ++pass) {  // the hidden layers of both branches, then the two heads
     for (int b = 0; b < 2; ++b) {
-      int fan_in = d->K * d->D;
+      int fan_in = fan_in0 ? fan_in0 : d->K * d->D;
       const int nl = b ? d->n_vf : d->n_pi;
       for (int l = 0; l <= nl; ++l) {  // l == nl: the branch's head
         const bool head = l == nl;

@@ -1,0 +1,507 @@
+// f16_policy_lma.h -- the LMA features extractor in front of the actor-critic MLPs as one HIP
+// kernel (gfx950), and the host side of f16env_policy_lma_blob_layout / f16env_policy_lma_forward
+// (include/f16env.h, ABI 7). Included by f16env.hip after f16_policy.h, whose policy_gemm /
+// policy_hidden / policy_tanh / policy_normals, operand forms and C/D register map it reuses.
+//
+// Tile: a block of 4 waves owns 32 observation rows. Every linear layer of the extractor is per
+// token, so it is the MLP's H^T = W X^T with the 32 rows as MFMA columns, once per token, and the
+// tokens are dealt to the waves (frame t and new token r to wave t % 4, r % 4): the serial chain of
+// ~70 small GEMMs per row tile, each waiting on L2 for its weights, becomes four chains side by
+// side. float32 throughout. Block barriers stand only between phases that exchange tokens: after
+// the second embedding, after k / v, and at the end of a block. The pi branch runs on wave 0, the
+// vf branch on wave 1. The block's LDS, in floats (L = L_new; images are [unit][row], row stride 32):
+//   zs   L x 1024   the residual stream z[r][unit][row]; after the blocks it is the features image
+//                   [r 32 + unit][row] the first MLP layers read
+//   kv   L x 2048   k and v of every token, each lane's own C/D registers (absent without blocks)
+//   vsh  32         the value head's output on its way from wave 1 to wave 0
+//   and per wave:
+//   ln   1024       a LayerNorm's output (the B operand of c_attn / c_fc)
+//   ao   1024       a token's attention output (the B operand of c_proj)
+//   S    max of     xf 18 x 33 + ys 64 x 32: one token's feature frame with its OWN zeroed pad row
+//                     (the 18th input has zero weights; it must not be another token's data:
+//                     0 x inf = NaN) and its embedding y[t]
+//                   ffh ff_hidden x 32: gelu(c_fc) of one token
+//                   hs  widest MLP layer x 32: a branch's hidden image
+// At most 159 872 B (L = 5): one block, four waves, per CU.
+// Stages 2-4 never form `flat`: token t is embedded alone, and k-step s of y[t] (channels 2 s,
+// 2 s + 1) is accumulated into the accumulator tile of the new token r it belongs to (rmap, from
+// the descriptor) against the k-step of W_2 that holds its two columns (cmap): dk and C_new are
+// even, so channels 2 s and 2 s + 1 are neighbours in `flat` and in one new token. A wave keeps its
+// frames' partial z[r] in at most 5 x 16 accumulator registers (wave 0's start from the bias); the
+// partials are added into zs in wave order, then relu.
+// Attention: the C/D map gives lane l, registers 4 hd .. 4 hd + 3 dims 4 (l >> 5) .. + 3 of head
+// hd of row l & 31, so q.k is four products and one add across lanes l and l ^ 32; q stays in
+// registers, k and v come back from the lane's own LDS slots. LayerNorm: a lane sums 16 units of
+// its row, the moments are one cross-lane add each (both lanes form a + b, the same bits).
+#pragma once
+
+namespace f16 {
+
+constexpr int LMA_MAX_L = 5;        // L_new at K = 10
+constexpr int LMA_MAX_LAYERS = 3;
+constexpr int LMA_EMBED = 64;       // D0
+constexpr int LMA_DNEW = 32;        // d_new: one output tile
+constexpr int LMA_FEAT = 17;        // features per frame
+constexpr int LMA_IMG = LMA_DNEW * POL_ROWS;  // floats of one [32 units][32 rows] image
+constexpr int LMA_XF = 608;         // 18 x 33 rounded up to a multiple of 16 floats
+constexpr int LMA_MAX_K = 10;
+constexpr int LMA_WAVES = 4;        // waves per block, all on the same 32 rows
+
+struct LmaBlockOps {
+  int32_t ln1_w, ln1_b, ln2_w, ln2_b;  // floats into the blob
+  PolicyOp q, kv, proj, fc, proj2;
+};
+struct LmaArgs {
+  const float* blob;
+  const float* obs;
+  const float* eps;
+  float* actions;
+  float* values;
+  float* log_probs;
+  float* features;
+  int64_t n, row_stride, frame_stride, id_base;
+  uint64_t seed, step;
+  int32_t K, L, n_layers, n_pi, n_vf, relu, flags, logstd_off, pe_off, w2_off, b2_off, kv_floats, s_floats;
+  PolicyOp we;
+  LmaBlockOps blk[LMA_MAX_LAYERS];
+  PolicyOp ops[POL_OPS];
+  uint8_t rmap[LMA_MAX_K * (LMA_EMBED / 2)];  // the new token r of k-step s of y[t]
+  uint8_t cmap[LMA_MAX_K * (LMA_EMBED / 2)];  // and its k-step of W_2 (column / 2)
+};
+
+__device__ __forceinline__ float lma_xor32(const float v) { return v + __shfl_xor(v, 32); }
+
+// out[unit][row] = LayerNorm(z[unit][row]) over the 32 units (eps 1e-5, the biased variance)
+__device__ __forceinline__ void lma_layernorm(const float* z, const float* __restrict__ w, const float* __restrict__ b,
+                                              float* out, const int lane) {
+  const int j = lane & 31, h = lane >> 5;
+  float x[16], s = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    x[i] = z[(16 * h + i) * POL_ROWS + j];
+    s += x[i];
+  }
+  const float mean = lma_xor32(s) * (1.0f / 32.0f);
+  float q = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    x[i] -= mean;
+    q += x[i] * x[i];
+  }
+  const float rstd = 1.0f / sqrtf(lma_xor32(q) * (1.0f / 32.0f) + 1e-5f);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) out[(16 * h + i) * POL_ROWS + j] = x[i] * rstd * w[16 * h + i] + b[16 * h + i];
+  __builtin_amdgcn_wave_barrier();
+}
+
+// z[unit][row] += acc (the residual update of one token)
+__device__ __forceinline__ void lma_residual(float* z, const pol_f32x16& acc, const int lane) {
+  const int j = lane & 31, h = lane >> 5;
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) z[pol_unit(r, h) * POL_ROWS + j] += acc[r];
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ffh[unit][row] = gelu(c_fc(ln)) in nn.GELU()'s exact form
+template <int TOUT>
+__device__ __forceinline__ void lma_fc(const float* __restrict__ wb, const PolicyOp op, const float* ln, float* ffh,
+                                       const int lane, pol_f32x16 (&acc)[4]) {
+  policy_gemm<TOUT>(wb, op, ln, POL_ROWS, lane, acc);
+  const int j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int to = 0; to < TOUT; ++to) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float v = acc[to][r];
+      ffh[(32 * to + pol_unit(r, h)) * POL_ROWS + j] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <int D>
+__global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(const LmaArgs a) {
+  extern __shared__ float4 lma_sm4[];
+  float* sm = reinterpret_cast<float*>(lma_sm4);
+  const int tid = (int)threadIdx.x, w = tid >> 6, lane = tid & 63, j = lane & 31, h = lane >> 5;
+  const float* wb = a.blob;
+  const int L = a.L;
+  const int64_t row0 = (int64_t)blockIdx.x * POL_ROWS;
+  const int64_t row = row0 + j;
+  const int64_t rowc = row < a.n ? row : a.n - 1;  // rows past n - 1 repeat it (always a valid read)
+  float* zs = sm;
+  float* kv = zs + L * LMA_IMG;
+  float* vsh = kv + a.kv_floats;
+  float* ln = vsh + POL_ROWS + w * (2 * LMA_IMG + a.s_floats);
+  float* ao = ln + LMA_IMG;
+  float* S = ao + LMA_IMG;
+  pol_f32x16 acc[4];
+
+  // ---- stages 1-4: features, embedding + PE, the stacking permutation folded into W_2
+  {
+    float* xf = S;
+    float* ys = S + LMA_XF;
+    pol_f32x16 zacc[LMA_MAX_L];
+    const float* b2 = wb + a.b2_off;
+#pragma unroll
+    for (int r = 0; r < LMA_MAX_L; ++r) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) zacc[r][q] = w == 0 ? b2[pol_unit(q, h)] : 0.0f;
+    }
+    if (h == 0) xf[LMA_FEAT * POL_XS + j] = 0.0f;  // the token's own zero-weight pad input
+    const float* pe = wb + a.pe_off;
+    for (int t = w; t < a.K; t += LMA_WAVES) {
+      if (h == 0) {
+        const float* o = a.obs + rowc * a.row_stride + (int64_t)t * a.frame_stride;
+        if (D == 15) {
+          float x[15], y[LMA_FEAT];
+#pragma unroll
+          for (int d = 0; d < 15; ++d) x[d] = o[d];
+          frame_features(x, y);
+#pragma unroll
+          for (int d = 0; d < LMA_FEAT; ++d) xf[d * POL_XS + j] = y[d];
+        } else {
+#pragma unroll
+          for (int d = 0; d < LMA_FEAT; ++d) xf[d * POL_XS + j] = o[d];
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      policy_gemm<2>(wb, a.we, xf, POL_XS, lane, acc);
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int to = 0; to < 2; ++to) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int u = 32 * to + pol_unit(q, h);
+          const float v = acc[to][q];
+          ys[u * POL_ROWS + j] = (v < 0.0f ? 0.0f : v) + pe[t * LMA_EMBED + u];
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      const float* wp = wb + a.w2_off + lane;
+      const float* yp = ys + h * POL_ROWS + j;
+      const uint8_t* rm = a.rmap + t * (LMA_EMBED / 2);
+      const uint8_t* cm = a.cmap + t * (LMA_EMBED / 2);
+      for (int s0 = 0; s0 < LMA_EMBED / 2; s0 += 8) {
+        float wv[8], b[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          wv[u] = wp[cm[s0 + u] * 64];
+          b[u] = yp[2 * (s0 + u) * POL_ROWS];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          switch (rm[s0 + u]) {  // (uniform: the accumulator tiles stay in registers)
+            case 0: zacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[u], b[u], zacc[0], 0, 0, 0); break;
+            case 1: zacc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[u], b[u], zacc[1], 0, 0, 0); break;
+            case 2: zacc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[u], b[u], zacc[2], 0, 0, 0); break;
+            case 3: zacc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[u], b[u], zacc[3], 0, 0, 0); break;
+            default: zacc[4] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[u], b[u], zacc[4], 0, 0, 0); break;
+          }
+        }
+      }
+      __builtin_amdgcn_wave_barrier();  // the next token's images follow every read of this one's
+    }
+    // z = relu(the waves' partial sums added in wave order): the bits depend on the descriptor alone
+    for (int ww = 0; ww < LMA_WAVES; ++ww) {
+      if (w == ww) {
+#pragma unroll
+        for (int r = 0; r < LMA_MAX_L; ++r) {
+          if (r < L) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+              float* p = zs + r * LMA_IMG + pol_unit(q, h) * POL_ROWS + j;
+              float v = zacc[r][q];
+              if (ww > 0) v += *p;
+              *p = (ww == LMA_WAVES - 1 && v < 0.0f) ? 0.0f : v;
+            }
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- the blocks
+  for (int layer = 0; layer < a.n_layers; ++layer) {
+    const LmaBlockOps B = a.blk[layer];
+    // k and v of every token, from the block's input z
+    for (int r = w; r < L; r += LMA_WAVES) {
+      lma_layernorm(zs + r * LMA_IMG, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
+      policy_gemm<2>(wb, B.kv, ln, POL_ROWS, lane, acc);
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        kv[(2 * r) * LMA_IMG + q * 64 + lane] = acc[0][q];
+        kv[(2 * r + 1) * LMA_IMG + q * 64 + lane] = acc[1][q];
+      }
+    }
+    __syncthreads();
+    // z[r] += c_proj(softmax(q[r] . k / sqrt(8)) v)
+    for (int r = w; r < L; r += LMA_WAVES) {
+      lma_layernorm(zs + r * LMA_IMG, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
+      policy_gemm<1>(wb, B.q, ln, POL_ROWS, lane, acc);
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int hd = 0; hd < 4; ++hd) {
+        float sc[LMA_MAX_L], m = -INFINITY;
+#pragma unroll
+        for (int b = 0; b < LMA_MAX_L; ++b) {
+          sc[b] = 0.0f;
+          if (b < L) {
+            const float* kp = kv + (2 * b) * LMA_IMG + (4 * hd) * 64 + lane;
+            float p = acc[0][4 * hd] * kp[0];
+            p += acc[0][4 * hd + 1] * kp[64];
+            p += acc[0][4 * hd + 2] * kp[128];
+            p += acc[0][4 * hd + 3] * kp[192];
+            sc[b] = lma_xor32(p) * 0.35355339059327373f;  // 1 / sqrt(8)
+            m = sc[b] > m ? sc[b] : m;
+          }
+        }
+        float sum = 0.0f;
+#pragma unroll
+        for (int b = 0; b < LMA_MAX_L; ++b) {
+          if (b < L) {
+            sc[b] = expf(sc[b] - m);
+            sum += sc[b];
+          }
+        }
+        const float inv = 1.0f / sum;
+        float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int b = 0; b < LMA_MAX_L; ++b) {
+          if (b < L) {
+            const float* vp = kv + (2 * b + 1) * LMA_IMG + (4 * hd) * 64 + lane;
+            const float p = sc[b] * inv;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] += p * vp[64 * i];
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ao[pol_unit(4 * hd + i, h) * POL_ROWS + j] = o[i];
+      }
+      __builtin_amdgcn_wave_barrier();
+      policy_gemm<1>(wb, B.proj, ao, POL_ROWS, lane, acc);
+      lma_residual(zs + r * LMA_IMG, acc[0], lane);
+    }
+    // z[r] += c_proj2(gelu(c_fc(LN2(z[r]))))
+    // (token r stays with its wave: no block barrier between the two residual updates)
+    float* ffh = S;
+    for (int r = w; r < L; r += LMA_WAVES) {
+      lma_layernorm(zs + r * LMA_IMG, wb + B.ln2_w, wb + B.ln2_b, ln, lane);
+      switch (B.fc.tout) {
+        case 1: lma_fc<1>(wb, B.fc, ln, ffh, lane, acc); break;
+        case 2: lma_fc<2>(wb, B.fc, ln, ffh, lane, acc); break;
+        case 3: lma_fc<3>(wb, B.fc, ln, ffh, lane, acc); break;
+        default: lma_fc<4>(wb, B.fc, ln, ffh, lane, acc); break;
+      }
+      policy_gemm<1>(wb, B.proj2, ffh, POL_ROWS, lane, acc);
+      lma_residual(zs + r * LMA_IMG, acc[0], lane);
+    }
+    __syncthreads();  // the next block's k / v follow every read of this one's
+  }
+
+  // ---- features_out: the flattened z, row-major (n, L 32)
+  if (a.features) {
+    const int F = L * LMA_DNEW;
+    for (int e = tid; e < POL_ROWS * F; e += 64 * LMA_WAVES) {
+      const int rj = e / F, f = e - rj * F;
+      if (row0 + rj < a.n) a.features[(row0 + rj) * F + f] = zs[f * POL_ROWS + rj];
+    }
+  }
+
+  // ---- the two MLPs on the features image, heads, sample and log-prob: f16_policy_forward_kernel's
+  // (wave 0 runs the pi branch, wave 1 the vf branch, each on its own hidden image)
+  float* hs = S;
+  float mean[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (w < 2 && !(w == 0 && (a.flags & F16_POLICY_VALUE_ONLY))) {
+    const int br = w;
+    const int base = br * (POL_MAX_LAYERS + 1);
+    const int nl = br ? a.n_vf : a.n_pi;
+    const float* xin = zs;
+    for (int l = 0; l < nl; ++l) {
+      const PolicyOp op = a.ops[base + l];
+      switch (op.tout) {
+        case 1: policy_hidden<1>(wb, op, xin, POL_ROWS, hs, a.relu, lane, acc); break;
+        case 2: policy_hidden<2>(wb, op, xin, POL_ROWS, hs, a.relu, lane, acc); break;
+        case 3: policy_hidden<3>(wb, op, xin, POL_ROWS, hs, a.relu, lane, acc); break;
+        default: policy_hidden<4>(wb, op, xin, POL_ROWS, hs, a.relu, lane, acc); break;
+      }
+      xin = hs;
+    }
+    policy_gemm<1>(wb, a.ops[base + POL_MAX_LAYERS], xin, POL_ROWS, lane, acc);
+    __builtin_amdgcn_wave_barrier();
+    if (br == 0) {
+      mean[0] = acc[0][0]; mean[1] = acc[0][1]; mean[2] = acc[0][2]; mean[3] = acc[0][3];
+    } else if (h == 0) {
+      vsh[j] = acc[0][0];
+    }
+  }
+  __syncthreads();
+  if (w != 0 || h != 0 || row >= a.n) return;
+  a.values[row] = vsh[j];
+  if (a.flags & F16_POLICY_VALUE_ONLY) return;
+  float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (!(a.flags & F16_POLICY_DETERMINISTIC)) {
+    if (a.eps) {
+      const float4 ev = reinterpret_cast<const float4*>(a.eps)[row];
+      e[0] = ev.x; e[1] = ev.y; e[2] = ev.z; e[3] = ev.w;
+    } else {
+      policy_normals(a.seed, (uint64_t)(a.id_base + row), a.step, e);
+    }
+  }
+  const float4 ls = *reinterpret_cast<const float4*>(wb + a.logstd_off);
+  const float lsv[4] = {ls.x, ls.y, ls.z, ls.w};
+  float av[4], lp = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    av[c] = mean[c] + expf(lsv[c]) * e[c];
+    lp += -0.5f * e[c] * e[c] - lsv[c] - 0.91893853320467274f;  // 0.5 log(2 pi)
+  }
+  reinterpret_cast<float4*>(a.actions)[row] = make_float4(av[0], av[1], av[2], av[3]);
+  a.log_probs[row] = lp;
+}
+
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+static const char* lma_desc_error(const f16_policy_desc* d, const f16_lma_desc* m) {
+  if (!m) return "null LMA descriptor";
+  if (m->K != d->K || m->D != d->D) return "lma K and D must equal the policy descriptor's";
+  if (m->embed_dim != LMA_EMBED) return "lma embed_dim must be 64";
+  const int hs = m->heads_stacking;
+  if (hs < 1 || LMA_EMBED % hs != 0 || ((LMA_EMBED / hs) & 1)) return "lma heads_stacking must divide embed_dim into an even dk";
+  if (m->d_new != LMA_DNEW) return "lma d_new must be 32";
+  if (m->heads_latent != 4) return "lma heads_latent must be 4";
+  if (m->ff_hidden != 32 && m->ff_hidden != 64 && m->ff_hidden != 96 && m->ff_hidden != 128)
+    return "lma ff_hidden must be 32, 64, 96 or 128";
+  if (m->n_layers < 0 || m->n_layers > LMA_MAX_LAYERS) return "lma n_layers must be in [0, 3]";
+  if (m->L_new < 1 || m->L_new > LMA_MAX_L || m->C_new < 2 || (m->C_new & 1) ||
+      (int64_t)m->L_new * m->C_new != (int64_t)m->K * LMA_EMBED)
+    return "lma L_new * C_new must equal K * embed_dim (L_new in [1, 5], C_new even)";
+  for (int i = 0; i < 6; ++i)
+    if (m->reserved[i] != 0) return "lma reserved fields must be zero";
+  return nullptr;
+}
+
+// f16env_policy_lma_blob_layout: the MLP pieces (first fan-in L_new d_new) and log_std as
+// policy_layout places them, then the extractor's pieces (include/f16env.h names the slots)
+static int64_t lma_layout(const f16_policy_desc* d, const f16_lma_desc* m, int64_t* off, LmaArgs* a) {
+  int64_t p = policy_layout(d, off, a ? a->ops : nullptr, m->L_new * m->d_new);
+  for (int i = F16_POLICY_N_OFFSETS; i < F16_LMA_N_OFFSETS; ++i) off[i] = -1;
+  auto put = [&](int slot, int64_t floats) {
+    off[slot] = p;
+    p += floats;
+    return (int32_t)off[slot];
+  };
+  const int nks_in = (LMA_FEAT + 1) / 2, nks_d = LMA_DNEW / 2, tff = m->ff_hidden / 32;
+  PolicyOp we, q, kv, proj, fc, proj2;
+  const int32_t pe = put(F16_LMA_OFF_PE, (int64_t)m->K * LMA_EMBED);
+  we.w_off = put(F16_LMA_OFF_WE_W, (LMA_EMBED / 32) * nks_in * 64);
+  we.b_off = put(F16_LMA_OFF_WE_B, LMA_EMBED);
+  we.nks = nks_in; we.tout = LMA_EMBED / 32;
+  const int32_t w2 = put(F16_LMA_OFF_W2_W, (m->C_new / 2) * 64);
+  const int32_t b2 = put(F16_LMA_OFF_W2_B, LMA_DNEW);
+  if (a) { a->pe_off = pe; a->we = we; a->w2_off = w2; a->b2_off = b2; }
+  for (int i = 0; i < m->n_layers; ++i) {
+    const int s = F16_LMA_OFF_BLOCK0 + F16_LMA_BLOCK_SLOTS * i;
+    LmaBlockOps B;
+    B.ln1_w = put(s + F16_LMA_BLK_LN1_W, LMA_DNEW);
+    B.ln1_b = put(s + F16_LMA_BLK_LN1_B, LMA_DNEW);
+    q.w_off = put(s + F16_LMA_BLK_ATTN_W, 3 * nks_d * 64);
+    q.b_off = put(s + F16_LMA_BLK_ATTN_B, 3 * LMA_DNEW);
+    q.nks = nks_d; q.tout = 1;
+    kv.w_off = q.w_off + nks_d * 64; kv.b_off = q.b_off + LMA_DNEW; kv.nks = nks_d; kv.tout = 2;
+    proj.w_off = put(s + F16_LMA_BLK_PROJ_W, nks_d * 64);
+    proj.b_off = put(s + F16_LMA_BLK_PROJ_B, LMA_DNEW);
+    proj.nks = nks_d; proj.tout = 1;
+    B.ln2_w = put(s + F16_LMA_BLK_LN2_W, LMA_DNEW);
+    B.ln2_b = put(s + F16_LMA_BLK_LN2_B, LMA_DNEW);
+    fc.w_off = put(s + F16_LMA_BLK_FC_W, tff * nks_d * 64);
+    fc.b_off = put(s + F16_LMA_BLK_FC_B, m->ff_hidden);
+    fc.nks = nks_d; fc.tout = tff;
+    proj2.w_off = put(s + F16_LMA_BLK_PROJ2_W, (m->ff_hidden / 2) * 64);
+    proj2.b_off = put(s + F16_LMA_BLK_PROJ2_B, LMA_DNEW);
+    proj2.nks = m->ff_hidden / 2; proj2.tout = 1;
+    B.q = q; B.kv = kv; B.proj = proj; B.fc = fc; B.proj2 = proj2;
+    if (a) a->blk[i] = B;
+  }
+  return p;
+}
+
+// The block's LDS in floats (the header comment's budget): zs, kv, the value row, and per wave ln,
+// ao and the widest phase of S (s_out)
+static int64_t lma_lds_floats(const f16_policy_desc* d, const f16_lma_desc* m, int32_t* kv_out, int32_t* s_out) {
+  int max_w = 32;
+  for (int l = 0; l < d->n_pi; ++l) max_w = d->pi_width[l] > max_w ? d->pi_width[l] : max_w;
+  for (int l = 0; l < d->n_vf; ++l) max_w = d->vf_width[l] > max_w ? d->vf_width[l] : max_w;
+  int32_t s = LMA_XF + LMA_EMBED * POL_ROWS;
+  if (m->n_layers > 0) s = m->ff_hidden * POL_ROWS > s ? m->ff_hidden * POL_ROWS : s;
+  s = max_w * POL_ROWS > s ? max_w * POL_ROWS : s;
+  const int32_t kv = m->n_layers > 0 ? 2 * m->L_new * LMA_IMG : 0;
+  *kv_out = kv;
+  *s_out = s;
+  return (int64_t)m->L_new * LMA_IMG + kv + POL_ROWS + (int64_t)LMA_WAVES * (2 * LMA_IMG + s);
+}
+
+static int policy_lma_forward_impl(void* stream, const f16_policy_desc* desc, const f16_lma_desc* m, const float* blob,
+                                   int64_t n, const float* obs, int64_t row_stride, int64_t frame_stride, uint64_t seed,
+                                   uint64_t step, int64_t id_base, const float* eps, float* actions, float* values,
+                                   float* log_probs, float* features_out, uint32_t flags) {
+  if (const char* e = policy_desc_error(desc)) return set_err(-1, e);
+  if (const char* e = lma_desc_error(desc, m)) return set_err(-1, e);
+  if (flags & ~(uint32_t)(F16_POLICY_DETERMINISTIC | F16_POLICY_VALUE_ONLY)) return set_err(-1, "unknown f16env_policy_lma_forward flags");
+  if (n < 0) return set_err(-1, "n must be >= 0");
+  const bool vonly = (flags & F16_POLICY_VALUE_ONLY) != 0;
+  LmaArgs a{};
+  int64_t off[F16_LMA_N_OFFSETS];
+  const int64_t nf = lma_layout(desc, m, off, &a);
+  if (nf > 0x7fffffffLL) return set_err(-1, "the blob is too large");
+  const int64_t lds = lma_lds_floats(desc, m, &a.kv_floats, &a.s_floats) * 4;
+  if (lds > POL_LDS_BYTES) return set_err(-1, "the LMA policy's images do not fit the LDS");
+  const int dk = LMA_EMBED / m->heads_stacking;
+  for (int t = 0; t < m->K; ++t)
+    for (int s = 0; s < LMA_EMBED / 2; ++s) {
+      const int c = 2 * s, f = ((c / dk) * m->K + t) * dk + c % dk;
+      a.rmap[t * (LMA_EMBED / 2) + s] = (uint8_t)(f / m->C_new);
+      a.cmap[t * (LMA_EMBED / 2) + s] = (uint8_t)(f % m->C_new / 2);
+    }
+  const void* fn = desc->D == 15 ? (const void*)f16_policy_lma_forward_kernel<15> : (const void*)f16_policy_lma_forward_kernel<17>;
+  if (n > 0) {
+    if (!blob || !obs || !values || (!vonly && (!actions || !log_probs))) return set_err(-1, "null argument");
+    if (((uintptr_t)blob & 15) != 0) return set_err(-1, "the weight blob must be 16-byte aligned");
+    if (((uintptr_t)obs & 3) != 0 || ((uintptr_t)values & 3) != 0 || ((uintptr_t)log_probs & 3) != 0)
+      return set_err(-1, "obs, values and log_probs must be float-aligned");
+    if (!vonly && (((uintptr_t)actions & 15) != 0 || ((uintptr_t)eps & 15) != 0))
+      return set_err(-1, "actions and eps must be 16-byte aligned");
+    if (((uintptr_t)features_out & 15) != 0) return set_err(-1, "features_out must be 16-byte aligned");
+    if (row_stride < 0 || frame_stride < 0) return set_err(-1, "strides must be non-negative");
+  }
+  const int64_t blocks = (n + POL_ROWS - 1) / POL_ROWS;
+  if (blocks > 0x7fffffffLL) return set_err(-1, "n too large");
+  // (dynamic LDS above 64 KB: opted into once per instance and device, as f16env_policy_forward; n == 0 does only this)
+  static uint64_t prepared[2];
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  const int inst = desc->D == 17 ? 1 : 0;
+  if (dev < 0 || dev >= 64 || !(__atomic_load_n(&prepared[inst], __ATOMIC_ACQUIRE) >> dev & 1)) {
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_BYTES));
+    if (dev >= 0 && dev < 64) __atomic_fetch_or(&prepared[inst], 1ull << dev, __ATOMIC_RELEASE);
+  }
+  if (n == 0) return 0;
+  a.blob = blob; a.obs = obs; a.eps = vonly ? nullptr : eps;
+  a.actions = actions; a.values = values; a.log_probs = log_probs; a.features = features_out;
+  a.n = n; a.row_stride = row_stride; a.frame_stride = frame_stride; a.id_base = id_base;
+  a.seed = seed; a.step = step;
+  a.K = m->K; a.L = m->L_new; a.n_layers = m->n_layers;
+  a.n_pi = desc->n_pi; a.n_vf = desc->n_vf;
+  a.relu = desc->activation == F16_POLICY_ACT_RELU ? 1 : 0;
+  a.flags = (int32_t)flags;
+  a.logstd_off = (int32_t)off[F16_POLICY_OFF_LOG_STD];
+  void* kargs[] = {&a};
+  HIPCHK(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * LMA_WAVES), kargs, (size_t)lds, (hipStream_t)stream));
+  return 0;
+}
+
+}  // namespace f16

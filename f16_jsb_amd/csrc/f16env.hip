@@ -2564,6 +2564,7 @@ static EnvArgs env_args(const f16env* h) {
 }
 
 #include "f16_policy.h"
+#include "f16_policy_lma.h"
 #include "f16_ppo.h"
 #include "f16_ppo_am.h"
 
@@ -3664,6 +3665,24 @@ int f16env_policy_backward(void* stream, const f16_policy_desc* desc, const floa
                            void* workspace, int64_t workspace_bytes, int32_t max_blocks, float* grad_blob) {
   return policy_backward_impl(stream, desc, blob, n, obs, row_stride, frame_stride, d_mean, d_values, workspace,
                               workspace_bytes, max_blocks, grad_blob);
+}
+
+int f16env_policy_lma_blob_layout(const f16_policy_desc* desc, const int32_t* lma, int64_t* offsets_out,
+                                  int64_t* n_floats_out) {
+  const f16_lma_desc* m = reinterpret_cast<const f16_lma_desc*>(lma);
+  if (const char* e = policy_desc_error(desc)) return set_err(-1, e);
+  if (const char* e = lma_desc_error(desc, m)) return set_err(-1, e);
+  if (!offsets_out || !n_floats_out) return set_err(-1, "null argument");
+  *n_floats_out = lma_layout(desc, m, offsets_out, nullptr);
+  return 0;
+}
+
+int f16env_policy_lma_forward(void* stream, const f16_policy_desc* desc, const int32_t* lma, const float* blob, int64_t n,
+                              const float* obs, int64_t row_stride, int64_t frame_stride, uint64_t seed, uint64_t step,
+                              int64_t id_base, const float* eps, float* actions, float* values, float* log_probs,
+                              float* features_out, uint32_t flags) {
+  return policy_lma_forward_impl(stream, desc, reinterpret_cast<const f16_lma_desc*>(lma), blob, n, obs, row_stride,
+                                 frame_stride, seed, step, id_base, eps, actions, values, log_probs, features_out, flags);
 }
 
 int f16env_ppo_workspace(int64_t n, int32_t max_blocks, int64_t* bytes_out) {

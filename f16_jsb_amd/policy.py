@@ -75,10 +75,11 @@ def _pack_bias(b, rows):
     return p
 
 
-def pack_blob(desc, pi, vf, act_head, val_head, log_std) -> torch.Tensor:
+def pack_blob(desc, pi, vf, act_head, val_head, log_std, fan_in0=None) -> torch.Tensor:
     """The kernel's weight blob (f16env_policy_blob_layout) as one float32 tensor on the weights'
-    device, from lists of (W[out][in], b[out]) per branch, the two heads and log_std[4]."""
-    off, total = policy_blob_layout(desc)
+    device, from lists of (W[out][in], b[out]) per branch, the two heads and log_std[4]. fan_in0:
+    the first layers' fan-in when it is not K D (an LMA policy's MLPs read the extractor's features)."""
+    off, total = policy_blob_layout(desc, fan_in0)
     f32 = lambda t: torch.as_tensor(t).detach().to(torch.float32)  # noqa: E731
     pieces, pos = [], 0
 
@@ -92,7 +93,7 @@ def pack_blob(desc, pi, vf, act_head, val_head, log_std) -> torch.Tensor:
     for b, (layers, widths, n) in enumerate(((pi, desc.pi_width, desc.n_pi), (vf, desc.vf_width, desc.n_vf))):
         if len(layers) != n:
             raise ValueError("%s branch: %d layers given, descriptor has %d" % ("vf" if b else "pi", len(layers), n))
-        fan_in = desc.K * desc.D
+        fan_in = desc.K * desc.D if fan_in0 is None else int(fan_in0)
         for l, (w, bias) in enumerate(layers):
             w, bias = f32(w), f32(bias)
             if w.shape[0] != widths[l] or bias.numel() != widths[l]:
@@ -119,11 +120,11 @@ def pack_blob(desc, pi, vf, act_head, val_head, log_std) -> torch.Tensor:
     return blob
 
 
-def unpack_blob(desc, blob):
+def unpack_blob(desc, blob, fan_in0=None):
     """The inverse of pack_blob, on the blob's device: (pi, vf, act_head, val_head, log_std) with
     pi / vf lists of (W[out][in], b[out]) and the heads at their true 4 / 1 rows. Copies, not
     views. A gradient in blob layout (pol.blob.grad) reads per layer the same way."""
-    off, total = policy_blob_layout(desc)
+    off, total = policy_blob_layout(desc, fan_in0)
     blob = torch.as_tensor(blob).detach()
     if blob.dim() != 1 or blob.numel() != total:
         raise ValueError("a blob of %d floats was expected, got shape %s" % (total, tuple(blob.shape)))
@@ -136,7 +137,7 @@ def unpack_blob(desc, blob):
 
     branches = []
     for b, (widths, n) in enumerate(((desc.pi_width, desc.n_pi), (desc.vf_width, desc.n_vf))):
-        layers, fan_in = [], desc.K * desc.D
+        layers, fan_in = [], desc.K * desc.D if fan_in0 is None else int(fan_in0)
         for l in range(n):
             layers.append(piece(6 * b + 2 * l, widths[l], widths[l], fan_in))
             fan_in = widths[l]

@@ -112,6 +112,9 @@ class DevicePPO:
                  max_grad_norm: float = 0.5, normalize_advantage: bool = True, betas=(0.9, 0.999), eps: float = 1e-5,
                  max_batch: int = 256, max_blocks: int = 0, am_ppo=None, optimizer: str = "adam", optimizer_kwargs=None):
         from ._lib import F16EnvError, fn
+        if hasattr(pol, "lma"):  # (before anything else: the refusal needs neither a GPU nor the library)
+            from .lma_policy import NO_BACKWARD
+            raise NotImplementedError("DevicePPO cannot train a DeviceLMAPolicy: " + NO_BACKWARD)
         if pol.device.type != "cuda":
             raise F16EnvError("DevicePPO runs on the GPU (f16env_ppo_loss_head, f16env_ppo_adam_step); the policy is "
                               "on %s and there is no fallback" % pol.device)

@@ -36,6 +36,8 @@
  *                      ActorCriticPolicy.forward with torch_layers.py MlpExtractor's separate pi / vf
  *                      MLPs and a DiagGaussianDistribution, one launch
  *   f16env_policy_backward <- loss.backward() through those two MLPs (ppo.py:391)
+ *   f16env_policy_lma_forward <- the same policy(obs_tensor) with train.py:21-32's
+ *                      StackedLMAFeaturesExtractor (jsbsim_gym/LMA_features.py) in front, eval mode
  *   f16env_ppo_loss_head <- ppo.py:355-388 (the clipped surrogate, value and entropy losses, the
  *                      statistics) and autograd through them down to (mean, values, log_std)
  *   f16env_ppo_adam_step <- ppo.py:392-395 clip_grad_norm_ and torch.optim.Adam.step, on the blob
@@ -79,7 +81,9 @@ extern "C" {
  * way.
  * Still 7: new f16env_ppo_dynago_workspace, f16env_ppo_dynago_update, f16env_ppo_loss_head_am and
  * f16env_ppo_dag_step (AM-PPO: the DynAGO controller, its loss head and the DAG / AlphaGrad step),
- * bound the same way. */
+ * bound the same way.
+ * Still 7: new f16_lma_desc, f16env_policy_lma_blob_layout and f16env_policy_lma_forward (the LMA
+ * features extractor in front of the two MLPs, forward only), bound the same way. */
 #define F16ENV_ABI_VERSION 7
 
 /* Frame layout (jsbsim_gym.py:12-25 STATE_FORMAT + goal, :172-197) */
@@ -621,6 +625,91 @@ int f16env_policy_backward_workspace(const f16_policy_desc* desc, int64_t n, int
 int f16env_policy_backward(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
                            int64_t row_stride, int64_t frame_stride, const float* d_mean, const float* d_values,
                            void* workspace, int64_t workspace_bytes, int32_t max_blocks, float* grad_blob);
+
+/* The LMA features extractor in front of the two MLPs (still ABI 7: two symbols added): the
+ * policy of the reference's train.py, features_extractor_class = StackedLMAFeaturesExtractor
+ * (jsbsim_gym/LMA_features.py), shared by actor and critic, in eval mode (dropout is the identity:
+ * collect_rollouts and predict run under set_training_mode(False)). Per observation row, with
+ * x[t] the 17 features of frame t (features.py:37-67 applied in the kernel when D = 15, the same
+ * expressions as f16env_features, so both input forms give the same bits; read as given when D = 17):
+ *   y[t] = relu(W_e x[t] + b_e) + PE[t]                 17 -> embed_dim (64); PE the (K, embed_dim)
+ *                                                       table of LMA_features.py:212-219, in the blob
+ *   flat[((c / dk) K + t) dk + c % dk] = y[t][c]        dk = embed_dim / heads_stacking (:241-275)
+ *   z[r] = relu(W_2 flat[r C_new .. (r + 1) C_new) + b_2)   r < L_new; C_new -> d_new (32)   (:278)
+ *   n_layers times (:403-407):
+ *     z += c_proj(attn(LN1(z)))    c_attn d_new -> 3 d_new = q | k | v, heads_latent (4) heads of 8
+ *                                  over the L_new tokens, softmax(q.k / sqrt(8)), no mask
+ *     z += c_proj2(gelu(c_fc(LN2(z))))   d_new -> ff_hidden -> d_new, gelu the exact erf form
+ *     LayerNorm: eps 1e-5, the biased variance
+ *   features = z flattened, (L_new d_new): the input of the pi / vf MLPs of `desc`, whose first
+ *   layers' fan-in is L_new d_new instead of K D. Heads, sample and log-prob as f16env_policy_forward.
+ * The descriptor is sixteen int32_t, passed by address (`lma` below points at an f16_lma_desc):
+ *   K, D            as desc's (they must agree)
+ *   embed_dim       64
+ *   heads_stacking  a divisor of embed_dim with dk even
+ *   L_new, C_new    the re-chunk: L_new the divisor of K embed_dim closest to max(K / 2, 1) (at a
+ *                   distance delta the candidate below is tried before the one above), C_new =
+ *                   K embed_dim / L_new; for embed_dim 64, K = 1..10: L_new 1 1 1 2 2 3 2 4 4 5,
+ *                   C_new 64 128 192 128 160 128 224 128 144 128. Checked: L_new C_new == K embed_dim,
+ *                   L_new <= 5, C_new even.
+ *   d_new 32; heads_latent 4; ff_hidden 32, 64, 96 or 128; n_layers 0..3; reserved[6] zero. */
+typedef struct f16_lma_desc_s {
+  int32_t K, D;
+  int32_t embed_dim, heads_stacking;
+  int32_t L_new, C_new;
+  int32_t d_new, heads_latent;
+  int32_t ff_hidden, n_layers;
+  int32_t reserved[6];
+} f16_lma_desc;
+
+/* The blob of an LMA policy (pure host function): offsets_out receives F16_LMA_N_OFFSETS offsets.
+ * Slots 0 .. F16_POLICY_N_OFFSETS - 1 are f16env_policy_blob_layout's, the MLP pieces in their
+ * packed form with a first-layer fan-in of L_new d_new, log_std included; the extractor's pieces
+ * follow log_std:
+ *   F16_LMA_OFF_PE      K x embed_dim floats, PE[t][c]
+ *   F16_LMA_OFF_WE_W/B  W_e (embed_dim x 17) in the operand form of f16env_policy_blob_layout
+ *                       ([out/32][ceil(in/2)][2][32], the 18th input zero), b_e
+ *   F16_LMA_OFF_W2_W/B  W_2 (d_new x C_new) in the same operand form, columns in torch's order (the
+ *                       kernel never forms `flat`: channels c = 2 s, 2 s + 1 of y[t] sit at
+ *                       f = ((c / dk) K + t) dk + c % dk and f + 1, so they meet k-step f % C_new / 2
+ *                       of W_2 in the accumulator of token f / C_new); b_2
+ *   F16_LMA_OFF_BLOCK0 + F16_LMA_BLOCK_SLOTS i + F16_LMA_BLK_*: block i's ln_1 weight, bias, c_attn
+ *                       (rows q, k, v as torch stores them) weight, bias, c_proj, ln_2, c_fc,
+ *                       mlp.c_proj; weights in the operand form, LN vectors d_new floats
+ * -1: the block does not exist. Every offset is a multiple of 4 floats. */
+#define F16_LMA_N_OFFSETS 58
+#define F16_LMA_OFF_PE 17
+#define F16_LMA_OFF_WE_W 18
+#define F16_LMA_OFF_WE_B 19
+#define F16_LMA_OFF_W2_W 20
+#define F16_LMA_OFF_W2_B 21
+#define F16_LMA_OFF_BLOCK0 22
+#define F16_LMA_BLOCK_SLOTS 12
+#define F16_LMA_BLK_LN1_W 0
+#define F16_LMA_BLK_LN1_B 1
+#define F16_LMA_BLK_ATTN_W 2
+#define F16_LMA_BLK_ATTN_B 3
+#define F16_LMA_BLK_PROJ_W 4
+#define F16_LMA_BLK_PROJ_B 5
+#define F16_LMA_BLK_LN2_W 6
+#define F16_LMA_BLK_LN2_B 7
+#define F16_LMA_BLK_FC_W 8
+#define F16_LMA_BLK_FC_B 9
+#define F16_LMA_BLK_PROJ2_W 10
+#define F16_LMA_BLK_PROJ2_B 11
+int f16env_policy_lma_blob_layout(const f16_policy_desc* desc, const int32_t* lma, int64_t* offsets_out,
+                                  int64_t* n_floats_out);
+
+/* One launch, the contract of f16env_policy_forward (strided obs read in place, rows [0, n) only,
+ * the flags, the POLICY NOISE stream, no sync, no allocation, capturable; n == 0 prepares the
+ * kernel instance; a bad argument returns < 0 before any launch), plus
+ *   features_out  NULL, or n x (L_new d_new) float, 16-B aligned: the extractor's output.
+ * A block of four waves owns 32 rows (tokens are dealt to the waves, their partial sums added in
+ * wave order); a row's outputs depend on neither the rows beside it nor n. */
+int f16env_policy_lma_forward(void* stream, const f16_policy_desc* desc, const int32_t* lma, const float* blob, int64_t n,
+                              const float* obs, int64_t row_stride, int64_t frame_stride, uint64_t seed, uint64_t step,
+                              int64_t id_base, const float* eps, float* actions, float* values, float* log_probs,
+                              float* features_out, uint32_t flags);
 
 /* The PPO minibatch update between the forward's (mean, values) and the new weights (still ABI 7:
  * four symbols added): the loss head, then -- after f16env_policy_backward has turned d_mean and
