@@ -11,7 +11,8 @@ from .abi import (F16C_N, F16_IC_N, F16_OBS_DIM, EnvConfig, config_default)  # n
 from .spaces import action_space, observation_space  # noqa: F401
 
 __all__ = ["F16Envs", "F16VecEnv", "F16GymVectorEnv", "F16GymEnv", "make", "make_vec", "reference_goal",
-           "config_default", "register_gymnasium", "DevicePolicy", "DevicePPO", "DeviceLMAPolicy"]
+           "config_default", "register_gymnasium", "DevicePolicy", "DevicePPO", "DeviceLMAPolicy",
+           "DeviceLMATrainPolicy"]
 
 ENV_ID = "JSBSim-v0"
 
@@ -23,9 +24,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
     if name == "DevicePolicy":
         from .policy import DevicePolicy
         return DevicePolicy
-    if name == "DeviceLMAPolicy":
-        from .lma_policy import DeviceLMAPolicy
-        return DeviceLMAPolicy
+    if name in ("DeviceLMAPolicy", "DeviceLMATrainPolicy"):
+        from . import lma_policy
+        return getattr(lma_policy, name)
     if name == "DevicePPO":
         from .ppo import DevicePPO
         return DevicePPO

@@ -80,6 +80,8 @@ SIGNATURES = {
     "f16env_policy_lma_blob_layout": (_i32, (_desc, _vp, _P(_i64), _P(_i64))),
     "f16env_policy_lma_forward": (_i32, (_vp, _desc, _vp, _vp, _i64, _vp, _i64, _i64, _u64, _u64, _i64, _vp, _vp, _vp,
                                          _vp, _vp, _u32)),
+    "f16env_policy_lma_backward_workspace": (_i32, (_desc, _vp, _i64, _i32, _P(_i64))),
+    "f16env_policy_lma_backward": (_i32, (_vp, _desc, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp)),
     "f16env_ppo_workspace": (_i32, (_i64, _i32, _P(_i64))),
     "f16env_ppo_head_blocks": (_i32, (_i64, _i32, _P(_i32))),
     "f16env_ppo_loss_head": (_i32, (_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _vp, _i64, _vp,

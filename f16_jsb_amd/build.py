@@ -23,6 +23,7 @@ OUT_O1 = os.path.join(HERE, "libf16env_o1.so")
 DEPS = [SRC, os.path.join(HERE, "csrc", "f16_device.h"), os.path.join(HERE, "csrc", "f16_tables.h"),
         os.path.join(HERE, "csrc", "f16_policy.h"), os.path.join(HERE, "csrc", "f16_ppo.h"),
         os.path.join(HERE, "csrc", "f16_ppo_am.h"), os.path.join(HERE, "csrc", "f16_policy_lma.h"),
+        os.path.join(HERE, "csrc", "f16_policy_lma_grad.h"),
         os.path.join(ROOT, "include", "f16env.h")]
 
 

@@ -2565,6 +2565,7 @@ static EnvArgs env_args(const f16env* h) {
 
 #include "f16_policy.h"
 #include "f16_policy_lma.h"
+#include "f16_policy_lma_grad.h"
 #include "f16_ppo.h"
 #include "f16_ppo_am.h"
 
@@ -3683,6 +3684,19 @@ int f16env_policy_lma_forward(void* stream, const f16_policy_desc* desc, const i
                               float* features_out, uint32_t flags) {
   return policy_lma_forward_impl(stream, desc, reinterpret_cast<const f16_lma_desc*>(lma), blob, n, obs, row_stride,
                                  frame_stride, seed, step, id_base, eps, actions, values, log_probs, features_out, flags);
+}
+
+int f16env_policy_lma_backward_workspace(const f16_policy_desc* desc, const int32_t* lma, int64_t n, int32_t max_blocks,
+                                         int64_t* bytes_out) {
+  return policy_lma_backward_workspace_impl(desc, reinterpret_cast<const f16_lma_desc*>(lma), n, max_blocks, bytes_out);
+}
+
+int f16env_policy_lma_backward(void* stream, const f16_policy_desc* desc, const int32_t* lma, const float* blob, int64_t n,
+                               const float* obs, int64_t row_stride, int64_t frame_stride, const float* d_mean,
+                               const float* d_values, void* workspace, int64_t workspace_bytes, int32_t max_blocks,
+                               float* grad_blob) {
+  return policy_lma_backward_impl(stream, desc, reinterpret_cast<const f16_lma_desc*>(lma), blob, n, obs, row_stride,
+                                  frame_stride, d_mean, d_values, workspace, workspace_bytes, max_blocks, grad_blob);
 }
 
 int f16env_ppo_workspace(int64_t n, int32_t max_blocks, int64_t* bytes_out) {

@@ -13,8 +13,15 @@ collect_rollouts and predict run under) as ONE HIP launch. It is a `DevicePolicy
     last_v, last_d = collect_rollout(envs, buf, policy_fn=pol)
     feats = pol.extract_features(envs.obs)          # (n, L_new * 32): what extract_features returns
 
-The backward of the extractor is not built: every gradient entry point, and DevicePPO, refuse an
-LMA policy by name rather than train the wrong thing.
+`DeviceLMAPolicy` is forward only: every gradient entry point refuses by name. The gradient is
+opt-in through `DeviceLMATrainPolicy` (f16env_policy_lma_backward): the same blob and forward, and
+the EVAL-MODE backward over it -- the reference's gradient at lma_dropout = 0.0, not at the 0.1 it
+trains with. DevicePPO refuses both classes until dropout is built.
+
+    pol = DeviceLMATrainPolicy.from_state_dict(sd, stack_k=10).requires_grad_()
+    opt = torch.optim.Adam(pol.parameters(), lr=3e-4, eps=1e-5)
+    v, log_prob, entropy = pol.evaluate_actions(mb.observations, mb.actions)
+    loss = ...; opt.zero_grad(); loss.backward(); clip_grad_norm_(pol.parameters(), 0.5); opt.step()
 """
 from __future__ import annotations
 
@@ -33,7 +40,8 @@ from .policy import (ACT_DIM, DevicePolicy, _pack_bias, _pack_weight, layers_fro
                      state_dict_from_layers, unpack_blob)
 
 NO_BACKWARD = ("the LMA backward is not built: DeviceLMAPolicy runs the rollout and predict forward only "
-               "(train the extractor in torch, then load_state_dict)")
+               "(train the extractor in torch, then load_state_dict; or opt in to the eval-mode gradient with "
+               "DeviceLMATrainPolicy)")
 EXTRACTOR = "features_extractor.lma_extractor."
 ALIASES = ("pi_features_extractor.", "vf_features_extractor.")
 # block piece -> (its module under lma_blocks.{i}., weight slot, bias slot, is a LayerNorm)
@@ -322,3 +330,29 @@ class DeviceLMAPolicy(DevicePolicy):
             ls = self.offsets[F16_POLICY_OFF_LOG_STD]
             dist = torch.distributions.Normal(mean, torch.ones_like(mean) * self.blob[ls:ls + ACT_DIM].exp())
             return values, dist.log_prob(actions).sum(dim=1), dist.entropy().sum(dim=1)
+
+
+class DeviceLMATrainPolicy(DeviceLMAPolicy):
+    """DeviceLMAPolicy with the eval-mode backward (f16env_policy_lma_backward): the same
+    constructors, blob and forward, so one object serves collect_rollout and the update.
+
+    This is the EVAL-MODE network: dropout is the identity in the forward and in the gradient, which
+    is therefore the reference's gradient at lma_dropout = 0.0 (the reference trains with 0.1; the
+    training-mode dropout is not built, and DevicePPO refuses this class as it refuses the parent).
+    The blob is the parameter; the PE table, log_std's slots of the kernel's gradient and every pad
+    receive +0 from the kernel (log_std's gradient reaches blob.grad through autograd's own slice
+    backward in evaluate_actions). An optimiser with weight decay would move the PE table: use none."""
+
+    # DevicePolicy's own gradient entry points in place of the parent's refusals: they differ only in
+    # the two symbols and in the second descriptor (backward_blob's +0 positions include the PE table)
+    _BWD = ("f16env_policy_lma_backward_workspace", "f16env_policy_lma_backward")
+
+    def _desc_args(self):
+        return (self._desc_ref, self._lma_ref)
+
+    parameters = DevicePolicy.parameters
+    requires_grad_ = DevicePolicy.requires_grad_
+    reserve_backward = DevicePolicy.reserve_backward
+    backward_blob = DevicePolicy.backward_blob
+    mean_and_value = DevicePolicy.mean_and_value
+    evaluate_actions = DevicePolicy.evaluate_actions

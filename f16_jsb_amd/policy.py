@@ -308,10 +308,17 @@ class DevicePolicy:
         """The blob's layers under SB3's key names (model.policy.load_state_dict(pol.state_dict()))."""
         return state_dict_from_layers(*unpack_blob(self.desc, self.blob))
 
+    # the backward's two entry points and the descriptor arguments both take (an LMA policy names its
+    # own pair and adds its second descriptor)
+    _BWD = ("f16env_policy_backward_workspace", "f16env_policy_backward")
+
+    def _desc_args(self):
+        return (self._desc_ref,)
+
     def _backward_fns(self):
         if self._bwd_fns is None:  # (taken at the first gradient: an older library still runs the forward)
             from ._lib import fn
-            self._bwd_fns = fn("f16env_policy_backward_workspace"), fn("f16env_policy_backward")
+            self._bwd_fns = fn(self._BWD[0]), fn(self._BWD[1])
         return self._bwd_fns
 
     def reserve_backward(self, n: int, max_blocks: int = 0):
@@ -320,7 +327,7 @@ class DevicePolicy:
         from ._lib import check
         ws_fn, bwd = self._backward_fns()
         need = ctypes.c_int64(0)
-        check(ws_fn(self._desc_ref, int(n), int(max_blocks), ctypes.byref(need)), "f16env_policy_backward_workspace")
+        check(ws_fn(*self._desc_args(), int(n), int(max_blocks), ctypes.byref(need)), self._BWD[0])
         have = getattr(self, "_bwd_ws", None)
         if have is None or have.numel() < need.value:
             if torch.cuda.is_current_stream_capturing():
@@ -328,8 +335,8 @@ class DevicePolicy:
                                    "reserve_backward(n, max_blocks) ahead of it")
             self._bwd_ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=self.device)
             with torch.cuda.device(self.device):
-                check(bwd(None, self._desc_ref, None, 0, None, 0, 0, None, None, None, 0, int(max_blocks), None),
-                      "f16env_policy_backward")
+                check(bwd(None, *self._desc_args(), None, 0, None, 0, 0, None, None, None, 0, int(max_blocks), None),
+                      self._BWD[1])
         return self._bwd_ws
 
     def backward_blob(self, obs, d_mean=None, d_values=None, max_blocks: int = 0, out=None):
@@ -353,10 +360,10 @@ class DevicePolicy:
         if n == 0:
             return out.zero_()
         ws = self.reserve_backward(n, max_blocks)
-        check(self._backward_fns()[1](stream_ptr(self.device), self._desc_ref, self.blob.data_ptr(), n, obs.data_ptr(),
+        check(self._backward_fns()[1](stream_ptr(self.device), *self._desc_args(), self.blob.data_ptr(), n, obs.data_ptr(),
                                       obs.stride(0), obs.stride(1), None if d_mean is None else d_mean.data_ptr(),
                                       None if d_values is None else d_values.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      int(max_blocks), out.data_ptr()), "f16env_policy_backward")
+                                      int(max_blocks), out.data_ptr()), self._BWD[1])
         return out
 
     def _mean_and_value(self, obs):

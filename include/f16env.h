@@ -38,6 +38,7 @@
  *   f16env_policy_backward <- loss.backward() through those two MLPs (ppo.py:391)
  *   f16env_policy_lma_forward <- the same policy(obs_tensor) with train.py:21-32's
  *                      StackedLMAFeaturesExtractor (jsbsim_gym/LMA_features.py) in front, eval mode
+ *   f16env_policy_lma_backward <- loss.backward() through that policy at lma_dropout = 0.0 (eval mode)
  *   f16env_ppo_loss_head <- ppo.py:355-388 (the clipped surrogate, value and entropy losses, the
  *                      statistics) and autograd through them down to (mean, values, log_std)
  *   f16env_ppo_adam_step <- ppo.py:392-395 clip_grad_norm_ and torch.optim.Adam.step, on the blob
@@ -83,7 +84,9 @@ extern "C" {
  * f16env_ppo_dag_step (AM-PPO: the DynAGO controller, its loss head and the DAG / AlphaGrad step),
  * bound the same way.
  * Still 7: new f16_lma_desc, f16env_policy_lma_blob_layout and f16env_policy_lma_forward (the LMA
- * features extractor in front of the two MLPs, forward only), bound the same way. */
+ * features extractor in front of the two MLPs, forward only), bound the same way.
+ * Still 7: new f16env_policy_lma_backward_workspace and f16env_policy_lma_backward (the eval-mode
+ * gradient of that policy's mean and value in the LMA blob's layout), bound the same way. */
 #define F16ENV_ABI_VERSION 7
 
 /* Frame layout (jsbsim_gym.py:12-25 STATE_FORMAT + goal, :172-197) */
@@ -710,6 +713,52 @@ int f16env_policy_lma_forward(void* stream, const f16_policy_desc* desc, const i
                               const float* obs, int64_t row_stride, int64_t frame_stride, uint64_t seed, uint64_t step,
                               int64_t id_base, const float* eps, float* actions, float* values, float* log_probs,
                               float* features_out, uint32_t flags);
+
+/* The eval-mode backward of the LMA policy, so that the reference's own network takes a gradient on
+ * the blob (still ABI 7: two symbols added). It is f16env_policy_backward's contract carried over to
+ * the LMA blob. With mean (n x 4) and value (n) what f16env_policy_lma_forward computes from (blob,
+ * obs) under F16_POLICY_DETERMINISTIC -- eval mode: dropout is the identity, i.e. the reference at
+ * lma_dropout = 0.0 -- and upstream gradients d_mean (n x 4 float, 16-B aligned), d_values (n float):
+ *   grad_blob[p] = sum_b ( d_mean[b] . d mean[b] / d blob[p] + d_values[b] d value[b] / d blob[p] )
+ * stored in f16env_policy_lma_blob_layout's own layout. The whole of grad_blob[0, n_floats) is
+ * overwritten, never accumulated into. Written as +0, always: every pad position (an odd fan-in's
+ * pad input, W_e's 18th input included; head rows and biases past 4 / 1), the four log_std slots,
+ * and the whole PE table (a constant of the reference, LMA_features.py:212-219, not a parameter).
+ * A NULL d_mean writes +0 over the pi branch's pieces (its hidden layers and the action head) and
+ * skips that branch's work; a NULL d_values does the same for the vf branch; the extractor then
+ * receives the other branch's gradient alone. Both NULL is an error.
+ * Derivatives, on recomputed forward values: tanh 1 - h*h; ReLU (the MLPs and both embeddings)
+ * h > 0 ? 1 : 0 (0 at 0, as torch); GELU in the exact form, Phi(x) + x phi(x); softmax
+ * P o (dP - sum P dP); LayerNorm with the biased variance, eps 1e-5 and both projection terms; the
+ * stacking permutation as the transpose of the forward's fold (d flat = W_2^T dz, read back at
+ * f = ((c / dk) K + t) dk + c % dk). No gradient with respect to obs is formed.
+ *   lma         the f16_lma_desc by address, as the forward; every descriptor the forward accepts
+ *   obs, row_stride, frame_stride   as f16env_policy_lma_forward
+ *   workspace   caller-owned device memory, 16-B aligned, at least the bytes
+ *               f16env_policy_lma_backward_workspace(desc, lma, n, max_blocks) states (a pure host
+ *               function, no device; monotone in n and in max_blocks): per block its partial
+ *               gradient (n_floats) and the checkpointed input of every extractor block
+ *               (n_layers x L_new x 32 x 33 floats)
+ *   max_blocks  limit of the grid; 0: the default (256). grid = min(ceil(n / 32), limit). A block is
+ *               one wave; it strides over the 32-row tiles, walks the whole network for a tile's
+ *               rows (up with a checkpoint per extractor block, down recomputing one block at a
+ *               time), accumulates its own partial in tile and token order, and a second launch
+ *               sums the partials in block order.
+ * Determinism: no atomics; the result's bits depend on (desc, lma, n, max_blocks) and the data
+ * alone, and two calls with the same arguments give the same bits. Rows past n - 1 of a last tile
+ * contribute exactly nothing. Nothing outside rows [0, n) of obs, d_mean, d_values is read; nothing
+ * outside grad_blob[0, n_floats) and the stated workspace bytes is written. No handle;
+ * stream-ordered; no sync and no allocation (safe under stream capture, after one call outside
+ * capture -- n == 0 suffices -- has prepared the kernel instance). n == 0 launches nothing and
+ * writes nothing. A bad argument (a bad descriptor, negative n or strides, a NULL or misaligned
+ * pointer, a workspace smaller than stated, max_blocks < 0, images that do not fit the LDS) returns
+ * < 0 with f16env_last_error set, before any launch. */
+int f16env_policy_lma_backward_workspace(const f16_policy_desc* desc, const int32_t* lma, int64_t n,
+                                         int32_t max_blocks, int64_t* bytes_out);
+int f16env_policy_lma_backward(void* stream, const f16_policy_desc* desc, const int32_t* lma, const float* blob,
+                               int64_t n, const float* obs, int64_t row_stride, int64_t frame_stride,
+                               const float* d_mean, const float* d_values, void* workspace,
+                               int64_t workspace_bytes, int32_t max_blocks, float* grad_blob);
 
 /* The PPO minibatch update between the forward's (mean, values) and the new weights (still ABI 7:
  * four symbols added): the loss head, then -- after f16env_policy_backward has turned d_mean and
