@@ -55,6 +55,18 @@ struct PolicyArgs {
 
 __device__ __forceinline__ int pol_unit(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// f(std::integral_constant<int, T>()) for the T = op.tout tiles (1..4) of a hidden layer: the one
+// place where a width of the descriptor picks a template instance
+template <class F>
+__device__ __forceinline__ void policy_tiles(const PolicyOp op, F&& f) {
+  switch (op.tout) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    default: f(std::integral_constant<int, 4>()); break;
+  }
+}
+
 // acc[to] = bias + W[to] X over nks k-steps (see the operand maps above)
 template <int TOUT>
 __device__ __forceinline__ void policy_gemm(const float* __restrict__ wb, const PolicyOp op, const float* xin,
@@ -160,6 +172,32 @@ __device__ __forceinline__ void policy_normals(uint64_t seed, uint64_t gid, uint
   e[3] = r2 * s4;
 }
 
+// A row's epilogue, by the lane that holds its action mean: eps from the caller, from the policy's
+// Philox stream, or zero (deterministic); action = mean + exp(log_std) eps and its log-prob, stored.
+// A: PolicyArgs or LmaArgs (the same fields); wb: where the kernel reads the blob.
+template <class A>
+__device__ __forceinline__ void policy_sample(const A& a, const float* wb, const int64_t row, const float (&mean)[4]) {
+  float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (!(a.flags & F16_POLICY_DETERMINISTIC)) {
+    if (a.eps) {
+      const float4 ev = reinterpret_cast<const float4*>(a.eps)[row];
+      e[0] = ev.x; e[1] = ev.y; e[2] = ev.z; e[3] = ev.w;
+    } else {
+      policy_normals(a.seed, (uint64_t)(a.id_base + row), a.step, e);
+    }
+  }
+  const float4 ls = *reinterpret_cast<const float4*>(wb + a.logstd_off);
+  const float lsv[4] = {ls.x, ls.y, ls.z, ls.w};
+  float av[4], lp = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    av[c] = mean[c] + expf(lsv[c]) * e[c];
+    lp += -0.5f * e[c] * e[c] - lsv[c] - 0.91893853320467274f;  // 0.5 log(2 pi)
+  }
+  reinterpret_cast<float4*>(a.actions)[row] = make_float4(av[0], av[1], av[2], av[3]);
+  a.log_probs[row] = lp;
+}
+
 template <int D, bool WLDS>
 __global__ __launch_bounds__(64 * POL_WAVES) void f16_policy_forward_kernel(const PolicyArgs a) {
   extern __shared__ float4 pol_sm4[];
@@ -229,12 +267,7 @@ __global__ __launch_bounds__(64 * POL_WAVES) void f16_policy_forward_kernel(cons
     int xstride = POL_XS;
     for (int l = 0; l < nl; ++l) {
       const PolicyOp op = a.ops[base + l];
-      switch (op.tout) {
-        case 1: policy_hidden<1>(wb, op, xin, xstride, hs, a.relu, lane, acc); break;
-        case 2: policy_hidden<2>(wb, op, xin, xstride, hs, a.relu, lane, acc); break;
-        case 3: policy_hidden<3>(wb, op, xin, xstride, hs, a.relu, lane, acc); break;
-        default: policy_hidden<4>(wb, op, xin, xstride, hs, a.relu, lane, acc); break;
-      }
+      policy_tiles(op, [&](auto t) { policy_hidden<decltype(t)::value>(wb, op, xin, xstride, hs, a.relu, lane, acc); });
       xin = hs;
       xstride = POL_ROWS;
     }
@@ -251,25 +284,7 @@ __global__ __launch_bounds__(64 * POL_WAVES) void f16_policy_forward_kernel(cons
   if (h != 0 || row >= a.n) return;
   a.values[row] = value;
   if (a.flags & F16_POLICY_VALUE_ONLY) return;
-  float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (!(a.flags & F16_POLICY_DETERMINISTIC)) {
-    if (a.eps) {
-      const float4 ev = reinterpret_cast<const float4*>(a.eps)[row];
-      e[0] = ev.x; e[1] = ev.y; e[2] = ev.z; e[3] = ev.w;
-    } else {
-      policy_normals(a.seed, (uint64_t)(a.id_base + row), a.step, e);
-    }
-  }
-  const float4 ls = *reinterpret_cast<const float4*>(wb + a.logstd_off);
-  const float lsv[4] = {ls.x, ls.y, ls.z, ls.w};
-  float av[4], lp = 0.0f;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    av[c] = mean[c] + expf(lsv[c]) * e[c];
-    lp += -0.5f * e[c] * e[c] - lsv[c] - 0.91893853320467274f;  // 0.5 log(2 pi)
-  }
-  reinterpret_cast<float4*>(a.actions)[row] = make_float4(av[0], av[1], av[2], av[3]);
-  a.log_probs[row] = lp;
+  policy_sample(a, wb, row, mean);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -294,6 +309,7 @@ __global__ __launch_bounds__(64 * POL_WAVES) void f16_policy_forward_kernel(cons
 // sums the slices that got a tile in slot order. No atomics: the bits depend on (desc, n,
 // max_blocks) alone.
 constexpr int POL_BWD_BLOCKS = 256;  // default grid limit: the MI355X's CU count
+constexpr int POL_OFF_VF0 = 6;       // policy_layout's slot of the vf branch's first hidden layer (6 b + 2 l, b = 1)
 
 struct PolicyBwdArgs {
   const float* blob;
@@ -361,13 +377,23 @@ __device__ __forceinline__ void policy_bwd_dw(float* g, const PolicyOp op, const
   }
 }
 
-// the slice's bias piece (+)= the delta image summed over the tile's rows, in row order
+// the 32 row values of one unit summed in row order (f16env_policy_backward's bias sum)
+struct PolicyRowSum {
+  __device__ __forceinline__ float operator()(const float* src) const {
+    float s = 0.0f;
+#pragma unroll
+    for (int r = 0; r < POL_ROWS; ++r) s += src[r];
+    return s;
+  }
+};
+
+// the slice's bias piece (+)= the delta image summed over the tile's rows by SUM (each backward
+// kernel keeps its own order of that sum: the bits differ)
+template <class SUM>
 __device__ __forceinline__ void policy_bwd_db(float* g, const PolicyOp op, const float* dl, const bool first,
                                               const int lane) {
   for (int u = lane; u < 32 * op.tout; u += 64) {
-    float s = 0.0f;
-#pragma unroll
-    for (int r = 0; r < POL_ROWS; ++r) s += dl[u * POL_XS + r];
+    const float s = SUM()(dl + u * POL_XS);
     float* p = g + op.b_off + u;
     *p = first ? s : *p + s;
   }
@@ -414,12 +440,64 @@ __device__ __forceinline__ void policy_bwd_delta(const float* __restrict__ wb, c
   __builtin_amdgcn_wave_barrier();
 }
 
+// One branch (br: 0 pi, 1 vf) of a tile's backward, from the first layers' input image x0 (stride
+// POL_XS): recompute the branch's activation images into `as`, write the head's delta into dl, then
+// for l = nl .. 0 the layer's dW and db (db summed by SUM) and, above layer 0, the delta of the layer
+// below. On return dl holds layer 0's delta: what it hands down, if anything, is the caller's.
+// A: PolicyBwdArgs or LmaBwdArgs (the same fields).
+template <class SUM, class A>
+__device__ __forceinline__ void policy_bwd_branch(const A& a, const int br, const float* x0, float* as, float* dl, float* g,
+                                                  const int64_t row, const bool valid, const bool first, const int lane,
+                                                  pol_f32x16 (&acc)[4]) {
+  const int j = lane & 31, h = lane >> 5;
+  const float* wb = a.blob;
+  const float* dout = br ? a.d_values : a.d_mean;
+  const int base = br * (POL_MAX_LAYERS + 1);
+  const int nl = br ? a.n_vf : a.n_pi;
+  // recompute the branch's activations, layer l into the image at as + 32 POL_XS (tiles below l)
+  {
+    const float* xin = x0;
+    float* hout = as;
+    for (int l = 0; l < nl; ++l) {
+      const PolicyOp op = a.ops[base + l];
+      policy_tiles(op, [&](auto t) { policy_bwd_hidden<decltype(t)::value>(wb, op, xin, hout, a.relu, lane, acc); });
+      xin = hout;
+      hout += 32 * op.tout * POL_XS;
+    }
+  }
+  // the head's delta: d_mean (units 0..3) or d_values (unit 0) of the rows inside n, zero elsewhere
+  {
+    float dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (valid && h == 0) {
+      if (br == 0) {
+        const float4 m = reinterpret_cast<const float4*>(dout)[row];
+        dv[0] = m.x; dv[1] = m.y; dv[2] = m.z; dv[3] = m.w;
+      } else {
+        dv[0] = dout[row];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) dl[(16 * h + q) * POL_XS + j] = q < 4 ? dv[q] : 0.0f;
+    __builtin_amdgcn_wave_barrier();
+  }
+  for (int l = nl; l >= 0; --l) {
+    const PolicyOp op = a.ops[base + (l == nl ? POL_MAX_LAYERS : l)];
+    int below = 0;  // tiles of the layers under layer l - 1: where its image starts
+    for (int m = 0; m + 1 < l; ++m) below += a.ops[base + m].tout;
+    const float* xin = l == 0 ? x0 : as + 32 * below * POL_XS;
+    policy_tiles(op, [&](auto t) { policy_bwd_dw<decltype(t)::value>(g, op, xin, dl, first, lane); });
+    policy_bwd_db<SUM>(g, op, dl, first, lane);
+    if (l == 0) break;
+    policy_tiles(a.ops[base + l - 1],
+                 [&](auto t) { policy_bwd_delta<decltype(t)::value>(wb, op, xin, dl, a.relu, valid, lane); });
+  }
+}
+
 template <int D>
 __global__ __launch_bounds__(64 * POL_WAVES) void f16_policy_backward_kernel(const PolicyBwdArgs a) {
   extern __shared__ float4 pol_sm4[];
   const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int j = lane & 31, h = lane >> 5;
-  const float* wb = a.blob;
+  const int j = lane & 31;
   float* xs = reinterpret_cast<float*>(pol_sm4) + wave * a.wave_floats;
   float* as = xs + a.obs_floats;
   float* dl = as + a.act_floats;
@@ -444,82 +522,44 @@ __global__ __launch_bounds__(64 * POL_WAVES) void f16_policy_backward_kernel(con
     const int64_t row = row0 + j;
     const bool valid = row < a.n;
 
-    for (int br = 0; br < 2; ++br) {
-      const float* dout = br ? a.d_values : a.d_mean;
-      if (!dout) continue;
-      const int base = br * (POL_MAX_LAYERS + 1);
-      const int nl = br ? a.n_vf : a.n_pi;
-      // recompute the branch's activations, layer l into the image at as + 32 POL_XS (tiles below l)
-      {
-        const float* xin = xs;
-        float* hout = as;
-        for (int l = 0; l < nl; ++l) {
-          const PolicyOp op = a.ops[base + l];
-          switch (op.tout) {
-            case 1: policy_bwd_hidden<1>(wb, op, xin, hout, a.relu, lane, acc); break;
-            case 2: policy_bwd_hidden<2>(wb, op, xin, hout, a.relu, lane, acc); break;
-            case 3: policy_bwd_hidden<3>(wb, op, xin, hout, a.relu, lane, acc); break;
-            default: policy_bwd_hidden<4>(wb, op, xin, hout, a.relu, lane, acc); break;
-          }
-          xin = hout;
-          hout += 32 * op.tout * POL_XS;
-        }
-      }
-      // the head's delta: d_mean (units 0..3) or d_values (unit 0) of the rows inside n, zero elsewhere
-      {
-        float dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (valid && h == 0) {
-          if (br == 0) {
-            const float4 m = reinterpret_cast<const float4*>(dout)[row];
-            dv[0] = m.x; dv[1] = m.y; dv[2] = m.z; dv[3] = m.w;
-          } else {
-            dv[0] = dout[row];
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) dl[(16 * h + q) * POL_XS + j] = q < 4 ? dv[q] : 0.0f;
-        __builtin_amdgcn_wave_barrier();
-      }
-      for (int l = nl; l >= 0; --l) {
-        const PolicyOp op = a.ops[base + (l == nl ? POL_MAX_LAYERS : l)];
-        int below = 0;  // tiles of the layers under layer l - 1: where its image starts
-        for (int m = 0; m + 1 < l; ++m) below += a.ops[base + m].tout;
-        const float* xin = l == 0 ? xs : as + 32 * below * POL_XS;
-        switch (op.tout) {
-          case 1: policy_bwd_dw<1>(g, op, xin, dl, first, lane); break;
-          case 2: policy_bwd_dw<2>(g, op, xin, dl, first, lane); break;
-          case 3: policy_bwd_dw<3>(g, op, xin, dl, first, lane); break;
-          default: policy_bwd_dw<4>(g, op, xin, dl, first, lane); break;
-        }
-        policy_bwd_db(g, op, dl, first, lane);
-        if (l == 0) break;  // no gradient to the observation
-        switch (a.ops[base + l - 1].tout) {
-          case 1: policy_bwd_delta<1>(wb, op, xin, dl, a.relu, valid, lane); break;
-          case 2: policy_bwd_delta<2>(wb, op, xin, dl, a.relu, valid, lane); break;
-          case 3: policy_bwd_delta<3>(wb, op, xin, dl, a.relu, valid, lane); break;
-          default: policy_bwd_delta<4>(wb, op, xin, dl, a.relu, valid, lane); break;
-        }
-      }
-    }
+    // (no gradient to the observation: the branch's backward ends after the first layer's dW and db)
+    for (int br = 0; br < 2; ++br)
+      if (br ? a.d_values : a.d_mean) policy_bwd_branch<PolicyRowSum>(a, br, xs, as, dl, g, row, valid, first, lane, acc);
     __builtin_amdgcn_wave_barrier();  // the next tile's staging follows every read of this one's images
     first = false;
   }
 }
 
-// grad[p] = the slices' sum in slot order; +0 at log_std (p >= logstd) and in a branch without an
-// upstream gradient (bit br of skip), whose slices nobody wrote
+// grad[p] = the slots' partials (slot_floats apart) summed in slot order. +0 where nothing is
+// trained: p in [zero0, zero1) (log_std to the blob's end for the MLP policy; log_std and the PE
+// table, neighbours in the LMA blob) and the MLP pieces of a branch without an upstream gradient
+// (bit br of skip), which no slot wrote.
 __global__ __launch_bounds__(256) void f16_policy_backward_reduce_kernel(const float* __restrict__ ws,
                                                                          float* __restrict__ grad, const int nf,
-                                                                         const int64_t nact, const int vf0,
-                                                                         const int act_w, const int val_w,
-                                                                         const int logstd, const int skip) {
+                                                                         const int64_t slot_floats, const int64_t nact,
+                                                                         const int vf0, const int act_w, const int val_w,
+                                                                         const int zero0, const int zero1, const int skip) {
   const int p = (int)(blockIdx.x * 256 + threadIdx.x);
   if (p >= nf) return;
-  const int br = p >= val_w ? 1 : (p >= act_w ? 0 : (p >= vf0 ? 1 : 0));
   float s = 0.0f;
-  if (p < logstd && !((skip >> br) & 1))
-    for (int64_t k = 0; k < nact; ++k) s += ws[k * nf + p];
+  bool sum = p < zero0 || p >= zero1;
+  if (p < zero0) {
+    const int br = p >= val_w ? 1 : (p >= act_w ? 0 : (p >= vf0 ? 1 : 0));
+    sum = !((skip >> br) & 1);
+  }
+  if (sum)
+    for (int64_t k = 0; k < nact; ++k) s += ws[k * slot_floats + p];
   grad[p] = s;
+}
+
+// both backward launchers' reduce: skip from the NULL upstream gradients, the branch boundaries from `off`
+static void policy_launch_reduce(hipStream_t stream, const float* ws, float* grad_blob, const int64_t nf,
+                                 const int64_t slot_floats, const int64_t nact, const int64_t* off, const int64_t zero1,
+                                 const float* d_mean, const float* d_values) {
+  const int skip = (d_mean ? 0 : 1) | (d_values ? 0 : 2);
+  hipLaunchKernelGGL(f16_policy_backward_reduce_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, ws,
+                     grad_blob, (int)nf, slot_floats, nact, (int)off[POL_OFF_VF0], (int)off[F16_POLICY_OFF_ACT_W],
+                     (int)off[F16_POLICY_OFF_VAL_W], (int)off[F16_POLICY_OFF_LOG_STD], (int)zero1, skip);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -576,23 +616,86 @@ static int64_t policy_layout(const f16_policy_desc* d, int64_t* off, PolicyOp* o
   return p + 4;
 }
 
+// the widest hidden layer (at least one tile) and each branch's sum of widths
+struct PolicyWidths {
+  int max_w, sum[2];
+};
+static PolicyWidths policy_widths(const f16_policy_desc* d) {
+  PolicyWidths w{32, {0, 0}};
+  for (int b = 0; b < 2; ++b)
+    for (int l = 0; l < (b ? d->n_vf : d->n_pi); ++l) {
+      const int x = b ? d->vf_width[l] : d->pi_width[l];
+      w.sum[b] += x;
+      w.max_w = x > w.max_w ? x : w.max_w;
+    }
+  return w;
+}
+
+// More than 64 KB of dynamic LDS is opted into once per kernel instance and device (word: the
+// instance's bit per device). A launcher does this and nothing else at n == 0: a caller about to
+// capture a graph prepares the instance ahead of it.
+static int policy_prepare_instance(const void* fn, uint64_t* word) {
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !(__atomic_load_n(word, __ATOMIC_ACQUIRE) >> dev & 1)) {
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_BYTES));
+    if (dev >= 0 && dev < 64) __atomic_fetch_or(word, 1ull << dev, __ATOMIC_RELEASE);
+  }
+  return 0;
+}
+
+// the arguments of the two forward entry points (entry: which one; features_out: the LMA's, else NULL)
+static int policy_forward_check(const char* entry, uint32_t flags, int64_t n, const float* blob, const float* obs,
+                                int64_t row_stride, int64_t frame_stride, const float* eps, const float* actions,
+                                const float* values, const float* log_probs, const float* features_out) {
+  if (flags & ~(uint32_t)(F16_POLICY_DETERMINISTIC | F16_POLICY_VALUE_ONLY))
+    return set_err(-1, (std::string("unknown ") + entry + " flags").c_str());
+  if (n < 0) return set_err(-1, "n must be >= 0");
+  if (n == 0) return 0;
+  const bool vonly = (flags & F16_POLICY_VALUE_ONLY) != 0;
+  if (!blob || !obs || !values || (!vonly && (!actions || !log_probs))) return set_err(-1, "null argument");
+  if (((uintptr_t)blob & 15) != 0) return set_err(-1, "the weight blob must be 16-byte aligned");
+  if (((uintptr_t)obs & 3) != 0 || ((uintptr_t)values & 3) != 0 || ((uintptr_t)log_probs & 3) != 0)
+    return set_err(-1, "obs, values and log_probs must be float-aligned");
+  if (!vonly && (((uintptr_t)actions & 15) != 0 || ((uintptr_t)eps & 15) != 0))
+    return set_err(-1, "actions and eps must be 16-byte aligned");
+  if (((uintptr_t)features_out & 15) != 0) return set_err(-1, "features_out must be 16-byte aligned");
+  if (row_stride < 0 || frame_stride < 0) return set_err(-1, "strides must be non-negative");
+  return 0;
+}
+
+// the arguments of the two backward entry points at n > 0 (ws_entry: the one that sizes the workspace)
+static int policy_backward_check(const char* ws_entry, const float* blob, const float* obs, int64_t row_stride,
+                                 int64_t frame_stride, const float* d_mean, const float* d_values, const void* workspace,
+                                 int64_t workspace_bytes, int64_t need_bytes, const float* grad_blob) {
+  if (!blob || !obs || !workspace || !grad_blob) return set_err(-1, "null argument");
+  if (!d_mean && !d_values) return set_err(-1, "d_mean and d_values are both NULL");
+  if (((uintptr_t)blob & 15) != 0 || ((uintptr_t)grad_blob & 15) != 0 || ((uintptr_t)d_mean & 15) != 0 ||
+      ((uintptr_t)workspace & 15) != 0)
+    return set_err(-1, "blob, grad_blob, d_mean and the workspace must be 16-byte aligned");
+  if (((uintptr_t)obs & 3) != 0 || ((uintptr_t)d_values & 3) != 0)
+    return set_err(-1, "obs and d_values must be float-aligned");
+  if (row_stride < 0 || frame_stride < 0) return set_err(-1, "strides must be non-negative");
+  if (workspace_bytes < need_bytes)
+    return set_err(-1, (std::string("the workspace is smaller than ") + ws_entry + " says").c_str());
+  return 0;
+}
+
 static int policy_forward_impl(void* stream, const f16_policy_desc* desc, const float* blob, int64_t n, const float* obs,
                                int64_t row_stride, int64_t frame_stride, uint64_t seed, uint64_t step, int64_t id_base,
                                const float* eps, float* actions, float* values, float* log_probs, uint32_t flags) {
   if (const char* m = policy_desc_error(desc)) return set_err(-1, m);
-  if (flags & ~(uint32_t)(F16_POLICY_DETERMINISTIC | F16_POLICY_VALUE_ONLY)) return set_err(-1, "unknown f16env_policy_forward flags");
-  if (n < 0) return set_err(-1, "n must be >= 0");
+  if (int rc = policy_forward_check("f16env_policy_forward", flags, n, blob, obs, row_stride, frame_stride, eps, actions,
+                                    values, log_probs, nullptr))
+    return rc;
   const bool vonly = (flags & F16_POLICY_VALUE_ONLY) != 0;
   PolicyArgs a{};
   int64_t off[F16_POLICY_N_OFFSETS];
   const int64_t nf = policy_layout(desc, off, a.ops);
-  int max_w = 32;
-  for (int l = 0; l < desc->n_pi; ++l) max_w = desc->pi_width[l] > max_w ? desc->pi_width[l] : max_w;
-  for (int l = 0; l < desc->n_vf; ++l) max_w = desc->vf_width[l] > max_w ? desc->vf_width[l] : max_w;
   a.K = desc->K;
   a.in_dim = desc->K * desc->D;
   a.obs_floats = (a.in_dim + (a.in_dim & 1)) * POL_XS;
-  a.hid_floats = max_w * POL_ROWS;
+  a.hid_floats = policy_widths(desc).max_w * POL_ROWS;
   a.blob_floats = (int32_t)nf;
   const int64_t tiles = (int64_t)POL_WAVES * (a.obs_floats + a.hid_floats) * 4;
   const bool wlds = nf * 4 + tiles <= POL_LDS_BYTES;
@@ -600,27 +703,10 @@ static int policy_forward_impl(void* stream, const f16_policy_desc* desc, const 
   const void* fn = desc->D == 15
       ? (wlds ? (const void*)f16_policy_forward_kernel<15, true> : (const void*)f16_policy_forward_kernel<15, false>)
       : (wlds ? (const void*)f16_policy_forward_kernel<17, true> : (const void*)f16_policy_forward_kernel<17, false>);
-  if (n > 0) {
-    if (!blob || !obs || !values || (!vonly && (!actions || !log_probs))) return set_err(-1, "null argument");
-    if (((uintptr_t)blob & 15) != 0) return set_err(-1, "the weight blob must be 16-byte aligned");
-    if (((uintptr_t)obs & 3) != 0 || ((uintptr_t)values & 3) != 0 || ((uintptr_t)log_probs & 3) != 0)
-      return set_err(-1, "obs, values and log_probs must be float-aligned");
-    if (!vonly && (((uintptr_t)actions & 15) != 0 || ((uintptr_t)eps & 15) != 0))
-      return set_err(-1, "actions and eps must be 16-byte aligned");
-    if (row_stride < 0 || frame_stride < 0) return set_err(-1, "strides must be non-negative");
-  }
   const int64_t blocks = (n + POL_WAVES * POL_ROWS - 1) / (POL_WAVES * POL_ROWS);
   if (blocks > 0x7fffffffLL) return set_err(-1, "n too large");
-  // more than 64 KB of dynamic LDS is opted into once per kernel instance and device (n == 0
-  // does only this: a caller about to capture a graph prepares the instance ahead of it)
   static uint64_t prepared[4];
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  const int inst = (desc->D == 17 ? 2 : 0) + (wlds ? 1 : 0);
-  if (dev < 0 || dev >= 64 || !(__atomic_load_n(&prepared[inst], __ATOMIC_ACQUIRE) >> dev & 1)) {
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_BYTES));
-    if (dev >= 0 && dev < 64) __atomic_fetch_or(&prepared[inst], 1ull << dev, __ATOMIC_RELEASE);
-  }
+  if (int rc = policy_prepare_instance(fn, &prepared[(desc->D == 17 ? 2 : 0) + (wlds ? 1 : 0)])) return rc;
   if (n == 0) return 0;
   a.blob = blob; a.obs = obs; a.eps = vonly ? nullptr : eps;
   a.actions = actions; a.values = values; a.log_probs = log_probs;
@@ -649,13 +735,11 @@ static int policy_bwd_plan(const f16_policy_desc* desc, int64_t n, int32_t max_b
   if (n < 0) return set_err(-1, "n must be >= 0");
   if (max_blocks < 0) return set_err(-1, "max_blocks must be >= 0 (0: the default)");
   p->nf = policy_layout(desc, off, ops);
-  int max_w = 32, sum[2] = {0, 0};
-  for (int l = 0; l < desc->n_pi; ++l) { sum[0] += desc->pi_width[l]; max_w = desc->pi_width[l] > max_w ? desc->pi_width[l] : max_w; }
-  for (int l = 0; l < desc->n_vf; ++l) { sum[1] += desc->vf_width[l]; max_w = desc->vf_width[l] > max_w ? desc->vf_width[l] : max_w; }
+  const PolicyWidths w = policy_widths(desc);
   const int in_dim = desc->K * desc->D;
   p->obs_floats = (in_dim + (in_dim & 1)) * POL_XS;
-  p->act_floats = (sum[0] > sum[1] ? sum[0] : sum[1]) * POL_XS;
-  p->wave_floats = p->obs_floats + p->act_floats + max_w * POL_XS;
+  p->act_floats = (w.sum[0] > w.sum[1] ? w.sum[0] : w.sum[1]) * POL_XS;
+  p->wave_floats = p->obs_floats + p->act_floats + w.max_w * POL_XS;
   const int64_t per_wave = (int64_t)p->wave_floats * 4;
   if (per_wave > POL_LDS_BYTES) return set_err(-1, "the policy's backward images do not fit the LDS for one wave");
   p->waves = 4 * per_wave <= POL_LDS_BYTES ? 4 : (2 * per_wave <= POL_LDS_BYTES ? 2 : 1);
@@ -681,28 +765,13 @@ static int policy_backward_impl(void* stream, const f16_policy_desc* desc, const
   PolicyBwdPlan p;
   int64_t off[F16_POLICY_N_OFFSETS];
   if (int rc = policy_bwd_plan(desc, n, max_blocks, &p, off, a.ops)) return rc;
-  if (n > 0) {
-    if (!blob || !obs || !workspace || !grad_blob) return set_err(-1, "null argument");
-    if (!d_mean && !d_values) return set_err(-1, "d_mean and d_values are both NULL");
-    if (((uintptr_t)blob & 15) != 0 || ((uintptr_t)grad_blob & 15) != 0 || ((uintptr_t)d_mean & 15) != 0 ||
-        ((uintptr_t)workspace & 15) != 0)
-      return set_err(-1, "blob, grad_blob, d_mean and the workspace must be 16-byte aligned");
-    if (((uintptr_t)obs & 3) != 0 || ((uintptr_t)d_values & 3) != 0)
-      return set_err(-1, "obs and d_values must be float-aligned");
-    if (row_stride < 0 || frame_stride < 0) return set_err(-1, "strides must be non-negative");
-    if (workspace_bytes < p.grid * p.waves * p.nf * 4)
-      return set_err(-1, "the workspace is smaller than f16env_policy_backward_workspace says");
-  }
+  if (n > 0)
+    if (int rc = policy_backward_check("f16env_policy_backward_workspace", blob, obs, row_stride, frame_stride, d_mean,
+                                       d_values, workspace, workspace_bytes, p.grid * p.waves * p.nf * 4, grad_blob))
+      return rc;
   const void* fn = desc->D == 15 ? (const void*)f16_policy_backward_kernel<15> : (const void*)f16_policy_backward_kernel<17>;
-  // (dynamic LDS above 64 KB: opted into once per instance and device, as the forward; n == 0 does only this)
   static uint64_t prepared[2];
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  const int inst = desc->D == 17 ? 1 : 0;
-  if (dev < 0 || dev >= 64 || !(__atomic_load_n(&prepared[inst], __ATOMIC_ACQUIRE) >> dev & 1)) {
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_BYTES));
-    if (dev >= 0 && dev < 64) __atomic_fetch_or(&prepared[inst], 1ull << dev, __ATOMIC_RELEASE);
-  }
+  if (int rc = policy_prepare_instance(fn, &prepared[desc->D == 17 ? 1 : 0])) return rc;
   if (n == 0) return 0;
   a.blob = blob; a.obs = obs; a.d_mean = d_mean; a.d_values = d_values;
   a.ws = static_cast<float*>(workspace);
@@ -717,11 +786,9 @@ static int policy_backward_impl(void* stream, const f16_policy_desc* desc, const
   void* kargs[] = {&a};
   HIPCHK(hipLaunchKernel(fn, dim3((unsigned)p.grid), dim3(64 * p.waves), kargs, (size_t)p.waves * p.wave_floats * 4,
                          (hipStream_t)stream));
-  const int64_t nact = p.ntiles < a.nslots ? p.ntiles : a.nslots;
-  const int skip = (d_mean ? 0 : 1) | (d_values ? 0 : 2);
-  hipLaunchKernelGGL(f16_policy_backward_reduce_kernel, dim3((unsigned)((p.nf + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, a.ws, grad_blob, (int)p.nf, nact, (int)off[6], (int)off[F16_POLICY_OFF_ACT_W],
-                     (int)off[F16_POLICY_OFF_VAL_W], (int)off[F16_POLICY_OFF_LOG_STD], skip);
+  // (the slots that got a tile; nothing from log_std to the blob's end is trained here)
+  policy_launch_reduce((hipStream_t)stream, a.ws, grad_blob, p.nf, p.nf, p.ntiles < a.nslots ? p.ntiles : a.nslots, off,
+                       p.nf, d_mean, d_values);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -1,7 +1,9 @@
 // f16_policy_lma.h -- the LMA features extractor in front of the actor-critic MLPs as one HIP
 // kernel (gfx950), and the host side of f16env_policy_lma_blob_layout / f16env_policy_lma_forward
 // (include/f16env.h, ABI 7). Included by f16env.hip after f16_policy.h, whose policy_gemm /
-// policy_hidden / policy_tanh / policy_normals, operand forms and C/D register map it reuses.
+// policy_hidden / policy_tiles / policy_sample, operand forms and C/D register map it reuses.
+// The extractor's pieces (lma_layernorm, lma_attention, lma_gelu, lma_embed_frame, lma_tile_out)
+// are written once here for this kernel and for the backward's recompute (f16_policy_lma_grad.h).
 //
 // Tile: a block of 4 waves owns 32 observation rows. Every linear layer of the extractor is per
 // token, so it is the MLP's H^T = W X^T with the 32 rows as MFMA columns, once per token, and the
@@ -46,12 +48,20 @@ constexpr int LMA_IMG = LMA_DNEW * POL_ROWS;  // floats of one [32 units][32 row
 constexpr int LMA_XF = 608;         // 18 x 33 rounded up to a multiple of 16 floats
 constexpr int LMA_MAX_K = 10;
 constexpr int LMA_WAVES = 4;        // waves per block, all on the same 32 rows
+constexpr float LMA_QK_SCALE = 0.35355339059327373f;  // 1 / sqrt(8): a latent head has 8 dims
 
 struct LmaBlockOps {
   int32_t ln1_w, ln1_b, ln2_w, ln2_b;  // floats into the blob
   PolicyOp q, kv, proj, fc, proj2;
 };
-struct LmaArgs {
+// where the extractor's and the MLPs' pieces lie in the blob: what lma_layout fills for both kernels
+struct LmaOps {
+  int32_t pe_off;
+  PolicyOp we, w2;
+  LmaBlockOps blk[LMA_MAX_LAYERS];
+  PolicyOp ops[POL_OPS];
+};
+struct LmaArgs : LmaOps {
   const float* blob;
   const float* obs;
   const float* eps;
@@ -61,49 +71,77 @@ struct LmaArgs {
   float* features;
   int64_t n, row_stride, frame_stride, id_base;
   uint64_t seed, step;
-  int32_t K, L, n_layers, n_pi, n_vf, relu, flags, logstd_off, pe_off, w2_off, b2_off, kv_floats, s_floats;
-  PolicyOp we;
-  LmaBlockOps blk[LMA_MAX_LAYERS];
-  PolicyOp ops[POL_OPS];
+  int32_t K, L, n_layers, n_pi, n_vf, relu, flags, logstd_off, kv_floats, s_floats;
   uint8_t rmap[LMA_MAX_K * (LMA_EMBED / 2)];  // the new token r of k-step s of y[t]
   uint8_t cmap[LMA_MAX_K * (LMA_EMBED / 2)];  // and its k-step of W_2 (column / 2)
 };
 
+// The shared pieces below serve the forward kernel (images at row stride POL_ROWS, k / v as each
+// lane's own C/D registers) and the backward's recompute (f16_policy_lma_grad.h: images at row
+// stride POL_XS): what differs is a template or ordinary parameter, the operations and their order
+// are one text, so both kernels round alike.
+
 __device__ __forceinline__ float lma_xor32(const float v) { return v + __shfl_xor(v, 32); }
 
-// out[unit][row] = LayerNorm(z[unit][row]) over the 32 units (eps 1e-5, the biased variance)
-__device__ __forceinline__ void lma_layernorm(const float* z, const float* __restrict__ w, const float* __restrict__ b,
-                                              float* out, const int lane) {
+// img[unit][row] (row stride STRIDE) = or += the accumulator tile
+template <int STRIDE, bool ADD>
+__device__ __forceinline__ void lma_tile_out(float* img, const pol_f32x16& acc, const int lane) {
   const int j = lane & 31, h = lane >> 5;
-  float x[16], s = 0.0f;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    float* p = img + pol_unit(q, h) * STRIDE + j;
+    if (ADD) *p += acc[q];
+    else *p = acc[q];
+  }
+}
+
+// a LayerNorm row's mean and 1 / sqrt(var + eps) over the 32 units (eps 1e-5, the biased variance);
+// x: the lane's 16 units less the mean. A lane sums 16 units, the moments are one cross-lane add each.
+template <int STRIDE>
+__device__ __forceinline__ void lma_ln_stats(const float* z, const int lane, float& mean, float& rstd, float (&x)[16]) {
+  const int j = lane & 31, h = lane >> 5;
+  float s = 0.0f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    x[i] = z[(16 * h + i) * POL_ROWS + j];
+    x[i] = z[(16 * h + i) * STRIDE + j];
     s += x[i];
   }
-  const float mean = lma_xor32(s) * (1.0f / 32.0f);
+  mean = lma_xor32(s) * (1.0f / 32.0f);
   float q = 0.0f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     x[i] -= mean;
     q += x[i] * x[i];
   }
-  const float rstd = 1.0f / sqrtf(lma_xor32(q) * (1.0f / 32.0f) + 1e-5f);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) out[(16 * h + i) * POL_ROWS + j] = x[i] * rstd * w[16 * h + i] + b[16 * h + i];
-  __builtin_amdgcn_wave_barrier();
+  rstd = 1.0f / sqrtf(lma_xor32(q) * (1.0f / 32.0f) + 1e-5f);
 }
 
-// z[unit][row] += acc (the residual update of one token)
-__device__ __forceinline__ void lma_residual(float* z, const pol_f32x16& acc, const int lane) {
+// out[unit][row] = LayerNorm(z[unit][row]), both images at row stride STRIDE
+template <int STRIDE>
+__device__ __forceinline__ void lma_layernorm(const float* z, const float* __restrict__ w, const float* __restrict__ b,
+                                              float* out, const int lane) {
   const int j = lane & 31, h = lane >> 5;
-  __builtin_amdgcn_wave_barrier();
+  float x[16], mean, rstd;
+  lma_ln_stats<STRIDE>(z, lane, mean, rstd, x);
 #pragma unroll
-  for (int r = 0; r < 16; ++r) z[pol_unit(r, h) * POL_ROWS + j] += acc[r];
+  for (int i = 0; i < 16; ++i) out[(16 * h + i) * STRIDE + j] = x[i] * rstd * w[16 * h + i] + b[16 * h + i];
   __builtin_amdgcn_wave_barrier();
 }
 
-// ffh[unit][row] = gelu(c_fc(ln)) in nn.GELU()'s exact form
+// z[unit][row] += acc (the forward's residual update of one token)
+__device__ __forceinline__ void lma_residual(float* z, const pol_f32x16& acc, const int lane) {
+  __builtin_amdgcn_wave_barrier();
+  lma_tile_out<POL_ROWS, true>(z, acc, lane);
+  __builtin_amdgcn_wave_barrier();
+}
+
+// nn.GELU()'s exact form, and d gelu / dv = Phi(v) + v phi(v)
+__device__ __forceinline__ float lma_gelu(const float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+__device__ __forceinline__ float lma_dgelu(const float v) {
+  return 0.5f * (1.0f + erff(v * 0.70710678118654752f)) + v * 0.3989422804014327f * expf(-0.5f * v * v);
+}
+
+// ffh[unit][row] = gelu(c_fc(ln))
 template <int TOUT>
 __device__ __forceinline__ void lma_fc(const float* __restrict__ wb, const PolicyOp op, const float* ln, float* ffh,
                                        const int lane, pol_f32x16 (&acc)[4]) {
@@ -112,11 +150,96 @@ __device__ __forceinline__ void lma_fc(const float* __restrict__ wb, const Polic
 #pragma unroll
   for (int to = 0; to < TOUT; ++to) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float v = acc[to][r];
-      ffh[(32 * to + pol_unit(r, h)) * POL_ROWS + j] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+    for (int r = 0; r < 16; ++r) ffh[(32 * to + pol_unit(r, h)) * POL_ROWS + j] = lma_gelu(acc[to][r]);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// Where a lane finds k and v of the tokens for its half of a head: dim i of head hd of token b is
+// k[b * pitch + hd * head + i * step] (v alike). The forward reads its own C/D registers back
+// (step 64, head 256); the backward reads [unit][row] images (step POL_XS, head 8 POL_XS).
+struct LmaKV {
+  const float* k;
+  const float* v;
+  int step, head, pitch;
+};
+
+// p = softmax(q . k / sqrt(8)) of head hd over the L tokens (q in the C/D registers: lanes l and
+// l ^ 32 hold four dims of the head each)
+__device__ __forceinline__ void lma_probs(const pol_f32x16& q, const LmaKV kv, const int L, const int hd,
+                                          float (&p)[LMA_MAX_L]) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int b = 0; b < LMA_MAX_L; ++b) {
+    p[b] = 0.0f;
+    if (b < L) {
+      const float* kp = kv.k + b * kv.pitch + hd * kv.head;
+      float s = q[4 * hd] * kp[0];
+      s += q[4 * hd + 1] * kp[kv.step];
+      s += q[4 * hd + 2] * kp[2 * kv.step];
+      s += q[4 * hd + 3] * kp[3 * kv.step];
+      p[b] = lma_xor32(s) * LMA_QK_SCALE;
+      m = p[b] > m ? p[b] : m;
     }
   }
+  float sum = 0.0f;
+#pragma unroll
+  for (int b = 0; b < LMA_MAX_L; ++b) {
+    if (b < L) {
+      p[b] = expf(p[b] - m);
+      sum += p[b];
+    }
+  }
+  const float inv = 1.0f / sum;
+#pragma unroll
+  for (int b = 0; b < LMA_MAX_L; ++b) p[b] *= inv;
+}
+
+// ao[unit][row] (row stride STRIDE) = softmax(q . k / sqrt(8)) v of one token
+template <int STRIDE>
+__device__ __forceinline__ void lma_attention(const pol_f32x16& q, const LmaKV kv, const int L, float* ao, const int lane) {
+  const int j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int hd = 0; hd < 4; ++hd) {
+    float p[LMA_MAX_L];
+    lma_probs(q, kv, L, hd, p);
+    float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int b = 0; b < LMA_MAX_L; ++b) {
+      if (b < L) {
+        const float* vp = kv.v + b * kv.pitch + hd * kv.head;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] += p[b] * vp[i * kv.step];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ao[pol_unit(4 * hd + i, h) * STRIDE + j] = o[i];
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// One frame of the tile's rows into xf[feature][row] (row stride POL_XS; lanes 0..31, one row
+// each: frame_features of a 15-wide frame, a copy of a 17-wide one; the pad row is the caller's)
+// and acc[0..1] = W_e x + b_e. o: the lane's row of the frame.
+template <int D>
+__device__ __forceinline__ void lma_embed_frame(const float* __restrict__ wb, const PolicyOp we, const float* o, float* xf,
+                                                const int lane, pol_f32x16 (&acc)[4]) {
+  const int j = lane & 31, h = lane >> 5;
+  if (h == 0) {
+    if (D == 15) {
+      float x[15], y[LMA_FEAT];
+#pragma unroll
+      for (int d = 0; d < 15; ++d) x[d] = o[d];
+      frame_features(x, y);
+#pragma unroll
+      for (int d = 0; d < LMA_FEAT; ++d) xf[d * POL_XS + j] = y[d];
+    } else {
+#pragma unroll
+      for (int d = 0; d < LMA_FEAT; ++d) xf[d * POL_XS + j] = o[d];
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  policy_gemm<2>(wb, we, xf, POL_XS, lane, acc);
   __builtin_amdgcn_wave_barrier();
 }
 
@@ -143,7 +266,7 @@ __global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(
     float* xf = S;
     float* ys = S + LMA_XF;
     pol_f32x16 zacc[LMA_MAX_L];
-    const float* b2 = wb + a.b2_off;
+    const float* b2 = wb + a.w2.b_off;
 #pragma unroll
     for (int r = 0; r < LMA_MAX_L; ++r) {
 #pragma unroll
@@ -152,23 +275,7 @@ __global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(
     if (h == 0) xf[LMA_FEAT * POL_XS + j] = 0.0f;  // the token's own zero-weight pad input
     const float* pe = wb + a.pe_off;
     for (int t = w; t < a.K; t += LMA_WAVES) {
-      if (h == 0) {
-        const float* o = a.obs + rowc * a.row_stride + (int64_t)t * a.frame_stride;
-        if (D == 15) {
-          float x[15], y[LMA_FEAT];
-#pragma unroll
-          for (int d = 0; d < 15; ++d) x[d] = o[d];
-          frame_features(x, y);
-#pragma unroll
-          for (int d = 0; d < LMA_FEAT; ++d) xf[d * POL_XS + j] = y[d];
-        } else {
-#pragma unroll
-          for (int d = 0; d < LMA_FEAT; ++d) xf[d * POL_XS + j] = o[d];
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      policy_gemm<2>(wb, a.we, xf, POL_XS, lane, acc);
-      __builtin_amdgcn_wave_barrier();
+      lma_embed_frame<D>(wb, a.we, a.obs + rowc * a.row_stride + (int64_t)t * a.frame_stride, xf, lane, acc);
 #pragma unroll
       for (int to = 0; to < 2; ++to) {
 #pragma unroll
@@ -179,7 +286,7 @@ __global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(
         }
       }
       __builtin_amdgcn_wave_barrier();
-      const float* wp = wb + a.w2_off + lane;
+      const float* wp = wb + a.w2.w_off + lane;
       const float* yp = ys + h * POL_ROWS + j;
       const uint8_t* rm = a.rmap + t * (LMA_EMBED / 2);
       const uint8_t* cm = a.cmap + t * (LMA_EMBED / 2);
@@ -228,7 +335,7 @@ __global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(
     const LmaBlockOps B = a.blk[layer];
     // k and v of every token, from the block's input z
     for (int r = w; r < L; r += LMA_WAVES) {
-      lma_layernorm(zs + r * LMA_IMG, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
+      lma_layernorm<POL_ROWS>(zs + r * LMA_IMG, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
       policy_gemm<2>(wb, B.kv, ln, POL_ROWS, lane, acc);
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -239,49 +346,12 @@ __global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(
     }
     __syncthreads();
     // z[r] += c_proj(softmax(q[r] . k / sqrt(8)) v)
+    const LmaKV own = {kv + lane, kv + LMA_IMG + lane, 64, 4 * 64, 2 * LMA_IMG};  // the lane's C/D registers back
     for (int r = w; r < L; r += LMA_WAVES) {
-      lma_layernorm(zs + r * LMA_IMG, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
+      lma_layernorm<POL_ROWS>(zs + r * LMA_IMG, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
       policy_gemm<1>(wb, B.q, ln, POL_ROWS, lane, acc);
       __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int hd = 0; hd < 4; ++hd) {
-        float sc[LMA_MAX_L], m = -INFINITY;
-#pragma unroll
-        for (int b = 0; b < LMA_MAX_L; ++b) {
-          sc[b] = 0.0f;
-          if (b < L) {
-            const float* kp = kv + (2 * b) * LMA_IMG + (4 * hd) * 64 + lane;
-            float p = acc[0][4 * hd] * kp[0];
-            p += acc[0][4 * hd + 1] * kp[64];
-            p += acc[0][4 * hd + 2] * kp[128];
-            p += acc[0][4 * hd + 3] * kp[192];
-            sc[b] = lma_xor32(p) * 0.35355339059327373f;  // 1 / sqrt(8)
-            m = sc[b] > m ? sc[b] : m;
-          }
-        }
-        float sum = 0.0f;
-#pragma unroll
-        for (int b = 0; b < LMA_MAX_L; ++b) {
-          if (b < L) {
-            sc[b] = expf(sc[b] - m);
-            sum += sc[b];
-          }
-        }
-        const float inv = 1.0f / sum;
-        float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int b = 0; b < LMA_MAX_L; ++b) {
-          if (b < L) {
-            const float* vp = kv + (2 * b + 1) * LMA_IMG + (4 * hd) * 64 + lane;
-            const float p = sc[b] * inv;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] += p * vp[64 * i];
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ao[pol_unit(4 * hd + i, h) * POL_ROWS + j] = o[i];
-      }
-      __builtin_amdgcn_wave_barrier();
+      lma_attention<POL_ROWS>(acc[0], own, L, ao, lane);
       policy_gemm<1>(wb, B.proj, ao, POL_ROWS, lane, acc);
       lma_residual(zs + r * LMA_IMG, acc[0], lane);
     }
@@ -289,13 +359,8 @@ __global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(
     // (token r stays with its wave: no block barrier between the two residual updates)
     float* ffh = S;
     for (int r = w; r < L; r += LMA_WAVES) {
-      lma_layernorm(zs + r * LMA_IMG, wb + B.ln2_w, wb + B.ln2_b, ln, lane);
-      switch (B.fc.tout) {
-        case 1: lma_fc<1>(wb, B.fc, ln, ffh, lane, acc); break;
-        case 2: lma_fc<2>(wb, B.fc, ln, ffh, lane, acc); break;
-        case 3: lma_fc<3>(wb, B.fc, ln, ffh, lane, acc); break;
-        default: lma_fc<4>(wb, B.fc, ln, ffh, lane, acc); break;
-      }
+      lma_layernorm<POL_ROWS>(zs + r * LMA_IMG, wb + B.ln2_w, wb + B.ln2_b, ln, lane);
+      policy_tiles(B.fc, [&](auto t) { lma_fc<decltype(t)::value>(wb, B.fc, ln, ffh, lane, acc); });
       policy_gemm<1>(wb, B.proj2, ffh, POL_ROWS, lane, acc);
       lma_residual(zs + r * LMA_IMG, acc[0], lane);
     }
@@ -311,8 +376,8 @@ __global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(
     }
   }
 
-  // ---- the two MLPs on the features image, heads, sample and log-prob: f16_policy_forward_kernel's
-  // (wave 0 runs the pi branch, wave 1 the vf branch, each on its own hidden image)
+  // ---- the two MLPs on the features image and the heads, as f16_policy_forward_kernel's (wave 0
+  // runs the pi branch, wave 1 the vf branch, each on its own hidden image), then policy_sample
   float* hs = S;
   float mean[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   if (w < 2 && !(w == 0 && (a.flags & F16_POLICY_VALUE_ONLY))) {
@@ -322,12 +387,7 @@ __global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(
     const float* xin = zs;
     for (int l = 0; l < nl; ++l) {
       const PolicyOp op = a.ops[base + l];
-      switch (op.tout) {
-        case 1: policy_hidden<1>(wb, op, xin, POL_ROWS, hs, a.relu, lane, acc); break;
-        case 2: policy_hidden<2>(wb, op, xin, POL_ROWS, hs, a.relu, lane, acc); break;
-        case 3: policy_hidden<3>(wb, op, xin, POL_ROWS, hs, a.relu, lane, acc); break;
-        default: policy_hidden<4>(wb, op, xin, POL_ROWS, hs, a.relu, lane, acc); break;
-      }
+      policy_tiles(op, [&](auto t) { policy_hidden<decltype(t)::value>(wb, op, xin, POL_ROWS, hs, a.relu, lane, acc); });
       xin = hs;
     }
     policy_gemm<1>(wb, a.ops[base + POL_MAX_LAYERS], xin, POL_ROWS, lane, acc);
@@ -342,25 +402,7 @@ __global__ __launch_bounds__(64 * LMA_WAVES) void f16_policy_lma_forward_kernel(
   if (w != 0 || h != 0 || row >= a.n) return;
   a.values[row] = vsh[j];
   if (a.flags & F16_POLICY_VALUE_ONLY) return;
-  float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (!(a.flags & F16_POLICY_DETERMINISTIC)) {
-    if (a.eps) {
-      const float4 ev = reinterpret_cast<const float4*>(a.eps)[row];
-      e[0] = ev.x; e[1] = ev.y; e[2] = ev.z; e[3] = ev.w;
-    } else {
-      policy_normals(a.seed, (uint64_t)(a.id_base + row), a.step, e);
-    }
-  }
-  const float4 ls = *reinterpret_cast<const float4*>(wb + a.logstd_off);
-  const float lsv[4] = {ls.x, ls.y, ls.z, ls.w};
-  float av[4], lp = 0.0f;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    av[c] = mean[c] + expf(lsv[c]) * e[c];
-    lp += -0.5f * e[c] * e[c] - lsv[c] - 0.91893853320467274f;  // 0.5 log(2 pi)
-  }
-  reinterpret_cast<float4*>(a.actions)[row] = make_float4(av[0], av[1], av[2], av[3]);
-  a.log_probs[row] = lp;
+  policy_sample(a, wb, row, mean);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -387,7 +429,7 @@ static const char* lma_desc_error(const f16_policy_desc* d, const f16_lma_desc* 
 
 // f16env_policy_lma_blob_layout: the MLP pieces (first fan-in L_new d_new) and log_std as
 // policy_layout places them, then the extractor's pieces (include/f16env.h names the slots)
-static int64_t lma_layout(const f16_policy_desc* d, const f16_lma_desc* m, int64_t* off, LmaArgs* a) {
+static int64_t lma_layout(const f16_policy_desc* d, const f16_lma_desc* m, int64_t* off, LmaOps* a) {
   int64_t p = policy_layout(d, off, a ? a->ops : nullptr, m->L_new * m->d_new);
   for (int i = F16_POLICY_N_OFFSETS; i < F16_LMA_N_OFFSETS; ++i) off[i] = -1;
   auto put = [&](int slot, int64_t floats) {
@@ -396,14 +438,15 @@ static int64_t lma_layout(const f16_policy_desc* d, const f16_lma_desc* m, int64
     return (int32_t)off[slot];
   };
   const int nks_in = (LMA_FEAT + 1) / 2, nks_d = LMA_DNEW / 2, tff = m->ff_hidden / 32;
-  PolicyOp we, q, kv, proj, fc, proj2;
+  PolicyOp we, w2, q, kv, proj, fc, proj2;
   const int32_t pe = put(F16_LMA_OFF_PE, (int64_t)m->K * LMA_EMBED);
   we.w_off = put(F16_LMA_OFF_WE_W, (LMA_EMBED / 32) * nks_in * 64);
   we.b_off = put(F16_LMA_OFF_WE_B, LMA_EMBED);
   we.nks = nks_in; we.tout = LMA_EMBED / 32;
-  const int32_t w2 = put(F16_LMA_OFF_W2_W, (m->C_new / 2) * 64);
-  const int32_t b2 = put(F16_LMA_OFF_W2_B, LMA_DNEW);
-  if (a) { a->pe_off = pe; a->we = we; a->w2_off = w2; a->b2_off = b2; }
+  w2.w_off = put(F16_LMA_OFF_W2_W, (m->C_new / 2) * 64);
+  w2.b_off = put(F16_LMA_OFF_W2_B, LMA_DNEW);
+  w2.nks = m->C_new / 2; w2.tout = 1;
+  if (a) { a->pe_off = pe; a->we = we; a->w2 = w2; }
   for (int i = 0; i < m->n_layers; ++i) {
     const int s = F16_LMA_OFF_BLOCK0 + F16_LMA_BLOCK_SLOTS * i;
     LmaBlockOps B;
@@ -430,12 +473,16 @@ static int64_t lma_layout(const f16_policy_desc* d, const f16_lma_desc* m, int64
   return p;
 }
 
+// the stacking permutation: where channel c of y[t] lies in `flat` (heads of dk channels, frames within a head)
+static int lma_flat_index(const f16_lma_desc* m, const int t, const int c) {
+  const int dk = LMA_EMBED / m->heads_stacking;
+  return ((c / dk) * m->K + t) * dk + c % dk;
+}
+
 // The block's LDS in floats (the header comment's budget): zs, kv, the value row, and per wave ln,
 // ao and the widest phase of S (s_out)
 static int64_t lma_lds_floats(const f16_policy_desc* d, const f16_lma_desc* m, int32_t* kv_out, int32_t* s_out) {
-  int max_w = 32;
-  for (int l = 0; l < d->n_pi; ++l) max_w = d->pi_width[l] > max_w ? d->pi_width[l] : max_w;
-  for (int l = 0; l < d->n_vf; ++l) max_w = d->vf_width[l] > max_w ? d->vf_width[l] : max_w;
+  const int max_w = policy_widths(d).max_w;
   int32_t s = LMA_XF + LMA_EMBED * POL_ROWS;
   if (m->n_layers > 0) s = m->ff_hidden * POL_ROWS > s ? m->ff_hidden * POL_ROWS : s;
   s = max_w * POL_ROWS > s ? max_w * POL_ROWS : s;
@@ -451,8 +498,9 @@ static int policy_lma_forward_impl(void* stream, const f16_policy_desc* desc, co
                                    float* log_probs, float* features_out, uint32_t flags) {
   if (const char* e = policy_desc_error(desc)) return set_err(-1, e);
   if (const char* e = lma_desc_error(desc, m)) return set_err(-1, e);
-  if (flags & ~(uint32_t)(F16_POLICY_DETERMINISTIC | F16_POLICY_VALUE_ONLY)) return set_err(-1, "unknown f16env_policy_lma_forward flags");
-  if (n < 0) return set_err(-1, "n must be >= 0");
+  if (int rc = policy_forward_check("f16env_policy_lma_forward", flags, n, blob, obs, row_stride, frame_stride, eps,
+                                    actions, values, log_probs, features_out))
+    return rc;
   const bool vonly = (flags & F16_POLICY_VALUE_ONLY) != 0;
   LmaArgs a{};
   int64_t off[F16_LMA_N_OFFSETS];
@@ -460,35 +508,17 @@ static int policy_lma_forward_impl(void* stream, const f16_policy_desc* desc, co
   if (nf > 0x7fffffffLL) return set_err(-1, "the blob is too large");
   const int64_t lds = lma_lds_floats(desc, m, &a.kv_floats, &a.s_floats) * 4;
   if (lds > POL_LDS_BYTES) return set_err(-1, "the LMA policy's images do not fit the LDS");
-  const int dk = LMA_EMBED / m->heads_stacking;
   for (int t = 0; t < m->K; ++t)
     for (int s = 0; s < LMA_EMBED / 2; ++s) {
-      const int c = 2 * s, f = ((c / dk) * m->K + t) * dk + c % dk;
+      const int f = lma_flat_index(m, t, 2 * s);
       a.rmap[t * (LMA_EMBED / 2) + s] = (uint8_t)(f / m->C_new);
       a.cmap[t * (LMA_EMBED / 2) + s] = (uint8_t)(f % m->C_new / 2);
     }
   const void* fn = desc->D == 15 ? (const void*)f16_policy_lma_forward_kernel<15> : (const void*)f16_policy_lma_forward_kernel<17>;
-  if (n > 0) {
-    if (!blob || !obs || !values || (!vonly && (!actions || !log_probs))) return set_err(-1, "null argument");
-    if (((uintptr_t)blob & 15) != 0) return set_err(-1, "the weight blob must be 16-byte aligned");
-    if (((uintptr_t)obs & 3) != 0 || ((uintptr_t)values & 3) != 0 || ((uintptr_t)log_probs & 3) != 0)
-      return set_err(-1, "obs, values and log_probs must be float-aligned");
-    if (!vonly && (((uintptr_t)actions & 15) != 0 || ((uintptr_t)eps & 15) != 0))
-      return set_err(-1, "actions and eps must be 16-byte aligned");
-    if (((uintptr_t)features_out & 15) != 0) return set_err(-1, "features_out must be 16-byte aligned");
-    if (row_stride < 0 || frame_stride < 0) return set_err(-1, "strides must be non-negative");
-  }
   const int64_t blocks = (n + POL_ROWS - 1) / POL_ROWS;
   if (blocks > 0x7fffffffLL) return set_err(-1, "n too large");
-  // (dynamic LDS above 64 KB: opted into once per instance and device, as f16env_policy_forward; n == 0 does only this)
   static uint64_t prepared[2];
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  const int inst = desc->D == 17 ? 1 : 0;
-  if (dev < 0 || dev >= 64 || !(__atomic_load_n(&prepared[inst], __ATOMIC_ACQUIRE) >> dev & 1)) {
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_BYTES));
-    if (dev >= 0 && dev < 64) __atomic_fetch_or(&prepared[inst], 1ull << dev, __ATOMIC_RELEASE);
-  }
+  if (int rc = policy_prepare_instance(fn, &prepared[desc->D == 17 ? 1 : 0])) return rc;
   if (n == 0) return 0;
   a.blob = blob; a.obs = obs; a.eps = vonly ? nullptr : eps;
   a.actions = actions; a.values = values; a.log_probs = log_probs; a.features = features_out;

@@ -1,8 +1,12 @@
 // f16_policy_lma_grad.h -- the eval-mode backward of the LMA policy in the blob's own layout
 // (f16env_policy_lma_backward, include/f16env.h ABI 7), one HIP kernel plus a reduce (gfx950).
-// Included by f16env.hip after f16_policy_lma.h: it reuses policy_gemm, the two products of
-// f16_policy_backward_kernel (policy_bwd_dw: dW^T = X^T Delta; the W^T Delta^T product as lmab_wt,
-// one input tile at a time) and the forward's C/D map of the attention. float32 throughout.
+// Included by f16env.hip after f16_policy_lma.h. It reuses, from f16_policy.h: policy_gemm, the
+// whole MLP branch of f16_policy_backward_kernel (policy_bwd_branch, with policy_bwd_dw: dW^T =
+// X^T Delta and policy_bwd_db summed pairwise; the W^T Delta^T product apart as lmab_wt, one input
+// tile at a time) and the reduce kernel; from f16_policy_lma.h, at the row stride POL_XS: the
+// forward's own lma_embed_frame, lma_layernorm / lma_ln_stats, lma_probs / lma_attention (k and v
+// addressed through LmaKV), lma_gelu / lma_dgelu and lma_tile_out, so the recompute rounds as the
+// forward kernel does. float32 throughout.
 //
 // Tile: ONE wave owns 32 observation rows and walks the whole network for them, every token in
 // turn; a block is that wave, a slot of the workspace is that block. So every slot owns every
@@ -41,39 +45,21 @@ namespace f16 {
 constexpr int LMAB_IMG = 32 * POL_XS;  // floats of one [32 units][33] image
 constexpr int LMAB_SCRATCH = 8;        // scratch images of the blocks phase
 constexpr int LMAB_BLOCKS = 256;       // default grid limit: the MI355X's CU count
-constexpr int LMAB_OFF_VF0 = 6;        // policy_layout's slot of the vf branch's first hidden layer (6 b + 2 l, b = 1)
 
-struct LmaBwdArgs {
+struct LmaBwdArgs : LmaOps {
   const float* blob;
   const float* obs;
   const float* d_mean;
   const float* d_values;
   float* ws;
   int64_t n, row_stride, frame_stride, ntiles, nslots, slot_floats;
-  int32_t K, L, C, n_layers, n_pi, n_vf, relu, nf, act_floats, pe_off;
-  PolicyOp we, w2;
-  LmaBlockOps blk[LMA_MAX_LAYERS];
-  PolicyOp ops[POL_OPS];
+  int32_t K, L, C, n_layers, n_pi, n_vf, relu, nf, act_floats;
   uint16_t fmap[LMA_MAX_K * (LMA_EMBED / 2)];  // flat index / 2 of channels 2 s, 2 s + 1 of y[t]
 };
 
 __device__ __forceinline__ void lmab_zero(pol_f32x16& a) {
 #pragma unroll
   for (int q = 0; q < 16; ++q) a[q] = 0.0f;
-}
-
-// img[unit][row] = the accumulator tile
-__device__ __forceinline__ void lmab_store(float* img, const pol_f32x16& acc, const int lane) {
-  const int j = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) img[pol_unit(q, h) * POL_XS + j] = acc[q];
-}
-
-// img[unit][row] += the accumulator tile
-__device__ __forceinline__ void lmab_add(float* img, const pol_f32x16& acc, const int lane) {
-  const int j = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) img[pol_unit(q, h) * POL_XS + j] += acc[q];
 }
 
 __host__ __device__ __forceinline__ PolicyOp lmab_op(const int32_t w_off, const int32_t b_off, const int32_t nks) {
@@ -84,56 +70,19 @@ __host__ __device__ __forceinline__ PolicyOp lmab_op(const int32_t w_off, const 
 
 // the 32 row values of one unit summed pairwise (neighbours, then pairs of pairs, ...): five
 // roundings deep instead of 31, the order torch's own reductions are closest to
-__device__ __forceinline__ float lmab_rowsum(const float* src) {
-  float v[POL_ROWS];
+struct LmabRowSum {
+  __device__ __forceinline__ float operator()(const float* src) const {
+    float v[POL_ROWS];
 #pragma unroll
-  for (int r = 0; r < POL_ROWS; ++r) v[r] = src[r];
+    for (int r = 0; r < POL_ROWS; ++r) v[r] = src[r];
 #pragma unroll
-  for (int w = 1; w < POL_ROWS; w *= 2) {
+    for (int w = 1; w < POL_ROWS; w *= 2) {
 #pragma unroll
-    for (int r = 0; r < POL_ROWS; r += 2 * w) v[r] += v[r + w];
+      for (int r = 0; r < POL_ROWS; r += 2 * w) v[r] += v[r + w];
+    }
+    return v[0];
   }
-  return v[0];
-}
-
-// the slice's bias piece (+)= the delta image summed over the tile's rows (policy_bwd_db with lmab_rowsum)
-__device__ __forceinline__ void lmab_db(float* g, const PolicyOp op, const float* dl, const bool first, const int lane) {
-  for (int u = lane; u < 32 * op.tout; u += 64) {
-    const float s = lmab_rowsum(dl + u * POL_XS);
-    float* p = g + op.b_off + u;
-    *p = first ? s : *p + s;
-  }
-}
-
-// a LayerNorm row's mean and 1 / sqrt(var + eps), summed as lma_layernorm sums them
-__device__ __forceinline__ void lmab_ln_stats(const float* z, const int lane, float& mean, float& rstd, float (&x)[16]) {
-  const int j = lane & 31, h = lane >> 5;
-  float s = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    x[i] = z[(16 * h + i) * POL_XS + j];
-    s += x[i];
-  }
-  mean = lma_xor32(s) * (1.0f / 32.0f);
-  float q = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    x[i] -= mean;
-    q += x[i] * x[i];
-  }
-  rstd = 1.0f / sqrtf(lma_xor32(q) * (1.0f / 32.0f) + 1e-5f);
-}
-
-// lma_layernorm on images of row stride POL_XS
-__device__ __forceinline__ void lmab_layernorm(const float* z, const float* __restrict__ w, const float* __restrict__ b,
-                                               float* out, const int lane) {
-  const int j = lane & 31, h = lane >> 5;
-  float x[16], mean, rstd;
-  lmab_ln_stats(z, lane, mean, rstd, x);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) out[(16 * h + i) * POL_XS + j] = x[i] * rstd * w[16 * h + i] + b[16 * h + i];
-  __builtin_amdgcn_wave_barrier();
-}
+};
 
 // The LayerNorm's backward. z: its input image; d: dL / d output in the C/D registers, replaced by
 // dL / dz = rstd (g - mean(g) - xhat mean(g xhat)), g = d w (both projection terms, the biased
@@ -143,7 +92,7 @@ __device__ __forceinline__ void lmab_ln_backward(const float* z, const float* __
                                                  const bool first, float* t0, float* t1, pol_f32x16& d, const int lane) {
   const int j = lane & 31, h = lane >> 5;
   float x[16], mean, rstd;
-  lmab_ln_stats(z, lane, mean, rstd, x);
+  lma_ln_stats<POL_XS>(z, lane, mean, rstd, x);
   float xh[16], sg = 0.0f, sgx = 0.0f;
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
@@ -162,7 +111,7 @@ __device__ __forceinline__ void lmab_ln_backward(const float* z, const float* __
   for (int q = 0; q < 16; ++q) d[q] = rstd * (d[q] - sg - xh[q] * sgx);
   __builtin_amdgcn_wave_barrier();
   {
-    const float s = lmab_rowsum((h ? t1 : t0) + j * POL_XS);
+    const float s = LmabRowSum()((h ? t1 : t0) + j * POL_XS);
     float* p = (h ? gw : gb) + j;
     *p = first ? s : *p + s;
   }
@@ -190,72 +139,21 @@ __device__ __forceinline__ void lmab_wt(const float* __restrict__ wb, const Poli
   }
 }
 
-// softmax(q . k / sqrt(8)) of head hd over the L tokens, op for op as the forward kernel
-__device__ __forceinline__ void lmab_probs(const pol_f32x16& q, const float* kv, const int L, const int hd, const int j,
-                                           const int h, float (&p)[LMA_MAX_L]) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int b = 0; b < LMA_MAX_L; ++b) {
-    p[b] = 0.0f;
-    if (b < L) {
-      const float* kp = kv + (2 * b) * LMAB_IMG + (8 * hd + 4 * h) * POL_XS + j;
-      float s = q[4 * hd] * kp[0];
-      s += q[4 * hd + 1] * kp[POL_XS];
-      s += q[4 * hd + 2] * kp[2 * POL_XS];
-      s += q[4 * hd + 3] * kp[3 * POL_XS];
-      p[b] = lma_xor32(s) * 0.35355339059327373f;  // 1 / sqrt(8)
-      m = p[b] > m ? p[b] : m;
-    }
-  }
-  float sum = 0.0f;
-#pragma unroll
-  for (int b = 0; b < LMA_MAX_L; ++b) {
-    if (b < L) {
-      p[b] = expf(p[b] - m);
-      sum += p[b];
-    }
-  }
-  const float inv = 1.0f / sum;
-#pragma unroll
-  for (int b = 0; b < LMA_MAX_L; ++b) p[b] *= inv;
-}
-
-// ao[unit][row] = softmax(q . k / sqrt(8)) v of one token (q in the C/D registers)
-__device__ __forceinline__ void lmab_attention(const pol_f32x16& q, const float* kv, const int L, float* ao, const int lane) {
-  const int j = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int hd = 0; hd < 4; ++hd) {
-    float p[LMA_MAX_L];
-    lmab_probs(q, kv, L, hd, j, h, p);
-    float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int b = 0; b < LMA_MAX_L; ++b) {
-      if (b < L) {
-        const float* vp = kv + (2 * b + 1) * LMAB_IMG + (8 * hd + 4 * h) * POL_XS + j;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] += p[b] * vp[i * POL_XS];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ao[(8 * hd + 4 * h + i) * POL_XS + j] = o[i];
-  }
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ float lmab_gelu(const float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
-// d gelu / dv = Phi(v) + v phi(v)
-__device__ __forceinline__ float lmab_dgelu(const float v) {
-  return 0.5f * (1.0f + erff(v * 0.70710678118654752f)) + v * 0.3989422804014327f * expf(-0.5f * v * v);
+// k and v of the tokens in the images kv ([2 b] k, [2 b + 1] v of token b) as a lane reads them:
+// its four dims of head hd are units 8 hd + 4 (l >> 5) .. + 3 of row l & 31 (the C/D map)
+__device__ __forceinline__ LmaKV lmab_kv_of(const float* kv, const int lane) {
+  const int o = 4 * (lane >> 5) * POL_XS + (lane & 31);
+  return {kv + o, kv + LMAB_IMG + o, POL_XS, 8 * POL_XS, 2 * LMAB_IMG};
 }
 
 // k and v of every token from the block's input z
 __device__ __forceinline__ void lmab_kv(const float* __restrict__ wb, const LmaBlockOps& B, const float* zs, float* kv,
                                         float* ln, const int L, const int lane, pol_f32x16 (&acc)[4]) {
   for (int r = 0; r < L; ++r) {
-    lmab_layernorm(zs + r * LMAB_IMG, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
+    lma_layernorm<POL_XS>(zs + r * LMAB_IMG, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
     policy_gemm<2>(wb, B.kv, ln, POL_XS, lane, acc);
-    lmab_store(kv + (2 * r) * LMAB_IMG, acc[0], lane);
-    lmab_store(kv + (2 * r + 1) * LMAB_IMG, acc[1], lane);
+    lma_tile_out<POL_XS, false>(kv + (2 * r) * LMAB_IMG, acc[0], lane);
+    lma_tile_out<POL_XS, false>(kv + (2 * r + 1) * LMAB_IMG, acc[1], lane);
     __builtin_amdgcn_wave_barrier();
   }
 }
@@ -269,22 +167,22 @@ __device__ __forceinline__ void lmab_block_forward(const float* __restrict__ wb,
   lmab_kv(wb, B, zs, kv, ln, L, lane, acc);
   for (int r = 0; r < L; ++r) {
     float* z = zs + r * LMAB_IMG;
-    lmab_layernorm(z, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
+    lma_layernorm<POL_XS>(z, wb + B.ln1_w, wb + B.ln1_b, ln, lane);
     policy_gemm<1>(wb, B.q, ln, POL_XS, lane, acc);
-    lmab_attention(acc[0], kv, L, ao, lane);
+    lma_attention<POL_XS>(acc[0], lmab_kv_of(kv, lane), L, ao, lane);
     policy_gemm<1>(wb, B.proj, ao, POL_XS, lane, acc);
-    lmab_add(z, acc[0], lane);
+    lma_tile_out<POL_XS, true>(z, acc[0], lane);
     __builtin_amdgcn_wave_barrier();
-    lmab_layernorm(z, wb + B.ln2_w, wb + B.ln2_b, ln, lane);
+    lma_layernorm<POL_XS>(z, wb + B.ln2_w, wb + B.ln2_b, ln, lane);
     for (int tt = 0; tt < B.fc.tout; ++tt) {
       policy_gemm<1>(wb, lmab_op(B.fc.w_off + tt * B.fc.nks * 64, B.fc.b_off + 32 * tt, B.fc.nks), ln, POL_XS, lane, acc);
 #pragma unroll
-      for (int q = 0; q < 16; ++q) acc[0][q] = lmab_gelu(acc[0][q]);
-      lmab_store(ffh + tt * LMAB_IMG, acc[0], lane);
+      for (int q = 0; q < 16; ++q) acc[0][q] = lma_gelu(acc[0][q]);
+      lma_tile_out<POL_XS, false>(ffh + tt * LMAB_IMG, acc[0], lane);
     }
     __builtin_amdgcn_wave_barrier();
     policy_gemm<1>(wb, B.proj2, ffh, POL_XS, lane, acc);
-    lmab_add(z, acc[0], lane);
+    lma_tile_out<POL_XS, true>(z, acc[0], lane);
     __builtin_amdgcn_wave_barrier();
   }
 }
@@ -312,10 +210,10 @@ __device__ __forceinline__ void lmab_block_backward(const float* __restrict__ wb
     const float* z = zs + r * LMAB_IMG;
     float* dzr = dz + r * LMAB_IMG;
     // recompute the attention half: LN1, q, the attention output, z after its residual update
-    lmab_layernorm(z, wb + B.ln1_w, wb + B.ln1_b, ln1, lane);
+    lma_layernorm<POL_XS>(z, wb + B.ln1_w, wb + B.ln1_b, ln1, lane);
     policy_gemm<1>(wb, B.q, ln1, POL_XS, lane, acc);
-    lmab_store(qs, acc[0], lane);
-    lmab_attention(acc[0], kv, L, ao, lane);
+    lma_tile_out<POL_XS, false>(qs, acc[0], lane);
+    lma_attention<POL_XS>(acc[0], lmab_kv_of(kv, lane), L, ao, lane);
     policy_gemm<1>(wb, B.proj, ao, POL_XS, lane, acc);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -326,7 +224,7 @@ __device__ __forceinline__ void lmab_block_backward(const float* __restrict__ wb
 
     // ---- the MLP half, one 32-unit tile of ff at a time: z_out = zm + c_proj2(gelu(c_fc(LN2(zm))))
     float* ln2 = s4;
-    lmab_layernorm(zm, wb + B.ln2_w, wb + B.ln2_b, ln2, lane);
+    lma_layernorm<POL_XS>(zm, wb + B.ln2_w, wb + B.ln2_b, ln2, lane);
     pol_f32x16 dln;
     lmab_zero(dln);
     for (int tt = 0; tt < B.fc.tout; ++tt) {
@@ -335,30 +233,30 @@ __device__ __forceinline__ void lmab_block_backward(const float* __restrict__ wb
       policy_gemm<1>(wb, fc, ln2, POL_XS, lane, acc);
       const pol_f32x16 pre = acc[0];
 #pragma unroll
-      for (int q = 0; q < 16; ++q) acc[0][q] = lmab_gelu(pre[q]);
-      lmab_store(s6, acc[0], lane);
+      for (int q = 0; q < 16; ++q) acc[0][q] = lma_gelu(pre[q]);
+      lma_tile_out<POL_XS, false>(s6, acc[0], lane);
       __builtin_amdgcn_wave_barrier();
       policy_bwd_dw<1>(g, p2, s6, dzr, f0, lane);
       pol_f32x16 d;
       lmab_zero(d);
       lmab_wt(wb, p2, 0, dzr, lane, d);
 #pragma unroll
-      for (int q = 0; q < 16; ++q) d[q] *= lmab_dgelu(pre[q]);
-      lmab_store(s7, d, lane);
+      for (int q = 0; q < 16; ++q) d[q] *= lma_dgelu(pre[q]);
+      lma_tile_out<POL_XS, false>(s7, d, lane);
       __builtin_amdgcn_wave_barrier();
       policy_bwd_dw<1>(g, fc, ln2, s7, f0, lane);
-      lmab_db(g, fc, s7, f0, lane);
+      policy_bwd_db<LmabRowSum>(g, fc, s7, f0, lane);
       lmab_wt(wb, fc, 0, s7, lane, dln);
       __builtin_amdgcn_wave_barrier();  // the next tile's images follow every read of this one's
     }
-    lmab_db(g, B.proj2, dzr, f0, lane);
+    policy_bwd_db<LmabRowSum>(g, B.proj2, dzr, f0, lane);
     lmab_ln_backward(zm, wb + B.ln2_w, g + B.ln2_w, g + B.ln2_b, f0, s5, s6, dln, lane);
-    lmab_add(dzr, dln, lane);  // now dL / d zm
+    lma_tile_out<POL_XS, true>(dzr, dln, lane);  // now dL / d zm
     __builtin_amdgcn_wave_barrier();
 
     // ---- the attention half: zm = z + c_proj(softmax(q . k / sqrt(8)) v)
     policy_bwd_dw<1>(g, B.proj, ao, dzr, f0, lane);
-    lmab_db(g, B.proj, dzr, f0, lane);
+    policy_bwd_db<LmabRowSum>(g, B.proj, dzr, f0, lane);
     pol_f32x16 dao, qv, dq;
     lmab_zero(dao);
     lmab_wt(wb, B.proj, 0, dzr, lane, dao);
@@ -370,7 +268,7 @@ __device__ __forceinline__ void lmab_block_backward(const float* __restrict__ wb
 #pragma unroll
     for (int hd = 0; hd < 4; ++hd) {
       float p[LMA_MAX_L], dp[LMA_MAX_L], dot = 0.0f;
-      lmab_probs(qv, kv, L, hd, j, h, p);
+      lma_probs(qv, lmab_kv_of(kv, lane), L, hd, p);
       const int o = (8 * hd + 4 * h) * POL_XS + j;
 #pragma unroll
       for (int b = 0; b < LMA_MAX_L; ++b) {
@@ -388,7 +286,7 @@ __device__ __forceinline__ void lmab_block_backward(const float* __restrict__ wb
 #pragma unroll
       for (int b = 0; b < LMA_MAX_L; ++b) {
         if (b < L) {
-          const float ds = p[b] * (dp[b] - dot) * 0.35355339059327373f;  // softmax: P o (dP - sum P dP)
+          const float ds = p[b] * (dp[b] - dot) * LMA_QK_SCALE;  // softmax: P o (dP - sum P dP)
           const float* kp = kv + (2 * b) * LMAB_IMG + o;
           float* dkp = dkv + (2 * b) * LMAB_IMG + o;
           float* dvp = dkv + (2 * b + 1) * LMAB_IMG + o;
@@ -401,14 +299,14 @@ __device__ __forceinline__ void lmab_block_backward(const float* __restrict__ wb
         }
       }
     }
-    lmab_store(s4, dq, lane);
+    lma_tile_out<POL_XS, false>(s4, dq, lane);
     __builtin_amdgcn_wave_barrier();
     policy_bwd_dw<1>(g, B.q, ln1, s4, f0, lane);
-    lmab_db(g, B.q, s4, f0, lane);
+    policy_bwd_db<LmabRowSum>(g, B.q, s4, f0, lane);
     lmab_zero(dln);
     lmab_wt(wb, B.q, 0, s4, lane, dln);
     lmab_ln_backward(z, wb + B.ln1_w, g + B.ln1_w, g + B.ln1_b, f0, s5, s6, dln, lane);
-    lmab_add(dzr, dln, lane);  // dL / dz through the residual and q; k and v follow below
+    lma_tile_out<POL_XS, true>(dzr, dln, lane);  // dL / dz through the residual and q; k and v follow below
     __builtin_amdgcn_wave_barrier();
   }
 
@@ -417,40 +315,16 @@ __device__ __forceinline__ void lmab_block_backward(const float* __restrict__ wb
     const bool f0 = first && b == 0;
     const float* z = zs + b * LMAB_IMG;
     const float* dkb = dkv + (2 * b) * LMAB_IMG;
-    lmab_layernorm(z, wb + B.ln1_w, wb + B.ln1_b, ln1, lane);
+    lma_layernorm<POL_XS>(z, wb + B.ln1_w, wb + B.ln1_b, ln1, lane);
     policy_bwd_dw<2>(g, B.kv, ln1, dkb, f0, lane);
-    lmab_db(g, B.kv, dkb, f0, lane);
+    policy_bwd_db<LmabRowSum>(g, B.kv, dkb, f0, lane);
     pol_f32x16 dln;
     lmab_zero(dln);
     lmab_wt(wb, B.kv, 0, dkb, lane, dln);
     lmab_ln_backward(z, wb + B.ln1_w, g + B.ln1_w, g + B.ln1_b, false, s5, s6, dln, lane);
-    lmab_add(dz + b * LMAB_IMG, dln, lane);
+    lma_tile_out<POL_XS, true>(dz + b * LMAB_IMG, dln, lane);
     __builtin_amdgcn_wave_barrier();
   }
-}
-
-// one frame's 17 features into xf (the pad row is the caller's) and acc[0..1] = W_e x + b_e
-template <int D>
-__device__ __forceinline__ void lmab_embed_frame(const LmaBwdArgs& a, const int t, const int64_t rowc, float* xf,
-                                                 const int lane, pol_f32x16 (&acc)[4]) {
-  const int j = lane & 31, h = lane >> 5;
-  if (h == 0) {
-    const float* o = a.obs + rowc * a.row_stride + (int64_t)t * a.frame_stride;
-    if (D == 15) {
-      float x[15], y[LMA_FEAT];
-#pragma unroll
-      for (int d = 0; d < 15; ++d) x[d] = o[d];
-      frame_features(x, y);
-#pragma unroll
-      for (int d = 0; d < LMA_FEAT; ++d) xf[d * POL_XS + j] = y[d];
-    } else {
-#pragma unroll
-      for (int d = 0; d < LMA_FEAT; ++d) xf[d * POL_XS + j] = o[d];
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  policy_gemm<2>(a.blob, a.we, xf, POL_XS, lane, acc);
-  __builtin_amdgcn_wave_barrier();
 }
 
 // `flat` of the tile's rows as an image [f][row]: y[t] = relu(W_e x[t] + b_e) + PE[t] at its place
@@ -462,7 +336,7 @@ __device__ __forceinline__ void lmab_flat(const LmaBwdArgs& a, const int64_t row
   const float* pe = a.blob + a.pe_off;
   if (h == 0) xf[LMA_FEAT * POL_XS + j] = 0.0f;  // the zero-weight pad input
   for (int t = 0; t < a.K; ++t) {
-    lmab_embed_frame<D>(a, t, rowc, xf, lane, acc);
+    lma_embed_frame<D>(a.blob, a.we, a.obs + rowc * a.row_stride + (int64_t)t * a.frame_stride, xf, lane, acc);
 #pragma unroll
     for (int to = 0; to < 2; ++to) {
 #pragma unroll
@@ -511,7 +385,7 @@ __global__ __launch_bounds__(64) void f16_policy_lma_backward_kernel(const LmaBw
       policy_gemm<1>(wb, a.w2, flat + r * C * POL_XS, POL_XS, lane, acc);
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[0][q] = acc[0][q] < 0.0f ? 0.0f : acc[0][q];
-      lmab_store(zs + r * LMAB_IMG, acc[0], lane);
+      lma_tile_out<POL_XS, false>(zs + r * LMAB_IMG, acc[0], lane);
     }
     __builtin_amdgcn_wave_barrier();
     for (int layer = 0; layer < a.n_layers; ++layer) {
@@ -524,69 +398,17 @@ __global__ __launch_bounds__(64) void f16_policy_lma_backward_kernel(const LmaBw
     // first layer also hands its delta down: dz = W^T Delta of both branches, pi first)
     bool have = false;
     for (int br = 0; br < 2; ++br) {
-      const float* dout = br ? a.d_values : a.d_mean;
-      if (!dout) continue;
-      const int base = br * (POL_MAX_LAYERS + 1);
-      const int nl = br ? a.n_vf : a.n_pi;
-      {
-        const float* xin = zs;
-        float* hout = as;
-        for (int l = 0; l < nl; ++l) {
-          const PolicyOp op = a.ops[base + l];
-          switch (op.tout) {
-            case 1: policy_bwd_hidden<1>(wb, op, xin, hout, a.relu, lane, acc); break;
-            case 2: policy_bwd_hidden<2>(wb, op, xin, hout, a.relu, lane, acc); break;
-            case 3: policy_bwd_hidden<3>(wb, op, xin, hout, a.relu, lane, acc); break;
-            default: policy_bwd_hidden<4>(wb, op, xin, hout, a.relu, lane, acc); break;
-          }
-          xin = hout;
-          hout += 32 * op.tout * POL_XS;
-        }
+      if (!(br ? a.d_values : a.d_mean)) continue;
+      policy_bwd_branch<LmabRowSum>(a, br, zs, as, dl, g, row, valid, first, lane, acc);
+      const PolicyOp op0 = a.ops[br * (POL_MAX_LAYERS + 1)];  // the branch's first layer: dl holds its delta
+      for (int ti = 0; ti < L; ++ti) {
+        pol_f32x16 d;
+        lmab_zero(d);
+        lmab_wt(wb, op0, ti, dl, lane, d);
+        if (have) lma_tile_out<POL_XS, true>(dz + ti * LMAB_IMG, d, lane);
+        else lma_tile_out<POL_XS, false>(dz + ti * LMAB_IMG, d, lane);
       }
-      {
-        float dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (valid && h == 0) {
-          if (br == 0) {
-            const float4 m = reinterpret_cast<const float4*>(dout)[row];
-            dv[0] = m.x; dv[1] = m.y; dv[2] = m.z; dv[3] = m.w;
-          } else {
-            dv[0] = dout[row];
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) dl[(16 * h + q) * POL_XS + j] = q < 4 ? dv[q] : 0.0f;
-        __builtin_amdgcn_wave_barrier();
-      }
-      for (int l = nl; l >= 0; --l) {
-        const PolicyOp op = a.ops[base + (l == nl ? POL_MAX_LAYERS : l)];
-        int below = 0;  // tiles of the layers under layer l - 1: where its image starts
-        for (int m = 0; m + 1 < l; ++m) below += a.ops[base + m].tout;
-        const float* xin = l == 0 ? zs : as + 32 * below * POL_XS;
-        switch (op.tout) {
-          case 1: policy_bwd_dw<1>(g, op, xin, dl, first, lane); break;
-          case 2: policy_bwd_dw<2>(g, op, xin, dl, first, lane); break;
-          case 3: policy_bwd_dw<3>(g, op, xin, dl, first, lane); break;
-          default: policy_bwd_dw<4>(g, op, xin, dl, first, lane); break;
-        }
-        lmab_db(g, op, dl, first, lane);
-        if (l == 0) {
-          for (int ti = 0; ti < L; ++ti) {
-            pol_f32x16 d;
-            lmab_zero(d);
-            lmab_wt(wb, op, ti, dl, lane, d);
-            if (have) lmab_add(dz + ti * LMAB_IMG, d, lane);
-            else lmab_store(dz + ti * LMAB_IMG, d, lane);
-          }
-          have = true;
-          break;
-        }
-        switch (a.ops[base + l - 1].tout) {
-          case 1: policy_bwd_delta<1>(wb, op, xin, dl, a.relu, valid, lane); break;
-          case 2: policy_bwd_delta<2>(wb, op, xin, dl, a.relu, valid, lane); break;
-          case 3: policy_bwd_delta<3>(wb, op, xin, dl, a.relu, valid, lane); break;
-          default: policy_bwd_delta<4>(wb, op, xin, dl, a.relu, valid, lane); break;
-        }
-      }
+      have = true;
       __builtin_amdgcn_wave_barrier();  // the other branch's images follow every read of this one's
     }
 
@@ -611,7 +433,7 @@ __global__ __launch_bounds__(64) void f16_policy_lma_backward_kernel(const LmaBw
       float* fr = flat + r * C * POL_XS;
       const float* dzr = dz + r * LMAB_IMG;
       policy_bwd_dw<1>(g, a.w2, fr, dzr, first && r == 0, lane);
-      lmab_db(g, a.w2, dzr, first && r == 0, lane);
+      policy_bwd_db<LmabRowSum>(g, a.w2, dzr, first && r == 0, lane);
       __builtin_amdgcn_wave_barrier();
       // d flat[r] = W_2^T dz[r] replaces flat[r]: the transpose of the forward's fold, read back per frame below
       for (int ti = 0; 32 * ti < C; ++ti) {
@@ -627,7 +449,7 @@ __global__ __launch_bounds__(64) void f16_policy_lma_backward_kernel(const LmaBw
       __builtin_amdgcn_wave_barrier();
     }
     for (int tf = 0; tf < a.K; ++tf) {
-      lmab_embed_frame<D>(a, tf, rowc, xf, lane, acc);
+      lma_embed_frame<D>(wb, a.we, a.obs + rowc * a.row_stride + (int64_t)tf * a.frame_stride, xf, lane, acc);
 #pragma unroll
       for (int to = 0; to < 2; ++to) {
 #pragma unroll
@@ -640,32 +462,11 @@ __global__ __launch_bounds__(64) void f16_policy_lma_backward_kernel(const LmaBw
       }
       __builtin_amdgcn_wave_barrier();
       policy_bwd_dw<2>(g, a.we, xf, ys, first && tf == 0, lane);
-      lmab_db(g, a.we, ys, first && tf == 0, lane);
+      policy_bwd_db<LmabRowSum>(g, a.we, ys, first && tf == 0, lane);
       __builtin_amdgcn_wave_barrier();  // the next frame's images follow every read of this one's
     }
     first = false;
   }
-}
-
-// grad[p] = the slots' partials summed in slot order. +0 where nothing is trained: log_std and the
-// PE table (p in [zero0, zero1): they are neighbours in the blob) and the MLP pieces of a branch
-// without an upstream gradient (bit br of skip), which no slot wrote.
-__global__ __launch_bounds__(256) void f16_policy_lma_backward_reduce_kernel(const float* __restrict__ ws,
-                                                                             float* __restrict__ grad, const int nf,
-                                                                             const int64_t slot_floats, const int64_t nact,
-                                                                             const int vf0, const int act_w, const int val_w,
-                                                                             const int zero0, const int zero1, const int skip) {
-  const int p = (int)(blockIdx.x * 256 + threadIdx.x);
-  if (p >= nf) return;
-  float s = 0.0f;
-  bool sum = p < zero0 || p >= zero1;
-  if (p < zero0) {
-    const int br = p >= val_w ? 1 : (p >= act_w ? 0 : (p >= vf0 ? 1 : 0));
-    sum = !((skip >> br) & 1);
-  }
-  if (sum)
-    for (int64_t k = 0; k < nact; ++k) s += ws[k * slot_floats + p];
-  grad[p] = s;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -680,26 +481,24 @@ struct LmaBwdPlan {
 // rule, the slot's floats (its partial gradient, then a checkpoint of L images per block), and
 // grid = min(tiles, max_blocks or LMAB_BLOCKS).
 static int lma_bwd_plan(const f16_policy_desc* desc, const f16_lma_desc* m, int64_t n, int32_t max_blocks, LmaBwdPlan* p,
-                        int64_t* off, LmaArgs* la) {
+                        int64_t* off, LmaOps* ops) {
   if (const char* e = policy_desc_error(desc)) return set_err(-1, e);
   if (const char* e = lma_desc_error(desc, m)) return set_err(-1, e);
   if (n < 0) return set_err(-1, "n must be >= 0");
   if (max_blocks < 0) return set_err(-1, "max_blocks must be >= 0 (0: the default)");
-  p->nf = lma_layout(desc, m, off, la);
+  p->nf = lma_layout(desc, m, off, ops);
   if (p->nf > 0x7fffffffLL) return set_err(-1, "the blob is too large");
   // what the reduce relies on: the blob is pi hidden | vf hidden | action head | value head | log_std | PE |
   // extractor with no gap between pieces (every float below log_std and past the PE table is a piece some
   // block writes: a gap would be summed from unwritten workspace), and log_std is followed at once by PE
-  if (off[0] != 0 || off[LMAB_OFF_VF0] <= 0 || off[LMAB_OFF_VF0] >= off[F16_POLICY_OFF_ACT_W] ||
+  if (off[0] != 0 || off[POL_OFF_VF0] <= 0 || off[POL_OFF_VF0] >= off[F16_POLICY_OFF_ACT_W] ||
       off[F16_POLICY_OFF_ACT_W] >= off[F16_POLICY_OFF_VAL_W] || off[F16_POLICY_OFF_VAL_W] >= off[F16_POLICY_OFF_LOG_STD] ||
       off[F16_LMA_OFF_PE] != off[F16_POLICY_OFF_LOG_STD] + 4 ||
       off[F16_LMA_OFF_WE_W] != off[F16_LMA_OFF_PE] + (int64_t)m->K * LMA_EMBED)
     return set_err(-1, "internal: the LMA blob layout is not the one the backward's reduce assumes");
-  int max_w = 32, sum[2] = {0, 0};
-  for (int l = 0; l < desc->n_pi; ++l) { sum[0] += desc->pi_width[l]; max_w = desc->pi_width[l] > max_w ? desc->pi_width[l] : max_w; }
-  for (int l = 0; l < desc->n_vf; ++l) { sum[1] += desc->vf_width[l]; max_w = desc->vf_width[l] > max_w ? desc->vf_width[l] : max_w; }
-  p->act_floats = (sum[0] > sum[1] ? sum[0] : sum[1]) * POL_XS;
-  const int64_t heads = p->act_floats + max_w * POL_XS;
+  const PolicyWidths w = policy_widths(desc);
+  p->act_floats = (w.sum[0] > w.sum[1] ? w.sum[0] : w.sum[1]) * POL_XS;
+  const int64_t heads = p->act_floats + w.max_w * POL_XS;
   const int64_t embed = (int64_t)m->K * LMA_EMBED * POL_XS + LMA_XF + 2 * LMAB_IMG;
   const int64_t blocks = m->n_layers > 0 ? (int64_t)(4 * m->L_new + LMAB_SCRATCH) * LMAB_IMG : 0;
   int64_t u = heads > embed ? heads : embed;
@@ -728,33 +527,17 @@ static int policy_lma_backward_impl(void* stream, const f16_policy_desc* desc, c
                                     const float* d_mean, const float* d_values, void* workspace, int64_t workspace_bytes,
                                     int32_t max_blocks, float* grad_blob) {
   LmaBwdPlan p;
-  LmaArgs la{};
-  int64_t off[F16_LMA_N_OFFSETS];
-  if (int rc = lma_bwd_plan(desc, m, n, max_blocks, &p, off, &la)) return rc;
-  if (n > 0) {
-    if (!blob || !obs || !workspace || !grad_blob) return set_err(-1, "null argument");
-    if (!d_mean && !d_values) return set_err(-1, "d_mean and d_values are both NULL");
-    if (((uintptr_t)blob & 15) != 0 || ((uintptr_t)grad_blob & 15) != 0 || ((uintptr_t)d_mean & 15) != 0 ||
-        ((uintptr_t)workspace & 15) != 0)
-      return set_err(-1, "blob, grad_blob, d_mean and the workspace must be 16-byte aligned");
-    if (((uintptr_t)obs & 3) != 0 || ((uintptr_t)d_values & 3) != 0)
-      return set_err(-1, "obs and d_values must be float-aligned");
-    if (row_stride < 0 || frame_stride < 0) return set_err(-1, "strides must be non-negative");
-    if (workspace_bytes < p.grid * p.slot_floats * 4)
-      return set_err(-1, "the workspace is smaller than f16env_policy_lma_backward_workspace says");
-  }
-  const void* fn = desc->D == 15 ? (const void*)f16_policy_lma_backward_kernel<15> : (const void*)f16_policy_lma_backward_kernel<17>;
-  // (dynamic LDS above 64 KB: opted into once per instance and device, as the forward; n == 0 does only this)
-  static uint64_t prepared[2];
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  const int inst = desc->D == 17 ? 1 : 0;
-  if (dev < 0 || dev >= 64 || !(__atomic_load_n(&prepared[inst], __ATOMIC_ACQUIRE) >> dev & 1)) {
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_BYTES));
-    if (dev >= 0 && dev < 64) __atomic_fetch_or(&prepared[inst], 1ull << dev, __ATOMIC_RELEASE);
-  }
-  if (n == 0) return 0;
   LmaBwdArgs a{};
+  int64_t off[F16_LMA_N_OFFSETS];
+  if (int rc = lma_bwd_plan(desc, m, n, max_blocks, &p, off, &a)) return rc;
+  if (n > 0)
+    if (int rc = policy_backward_check("f16env_policy_lma_backward_workspace", blob, obs, row_stride, frame_stride, d_mean,
+                                       d_values, workspace, workspace_bytes, p.grid * p.slot_floats * 4, grad_blob))
+      return rc;
+  const void* fn = desc->D == 15 ? (const void*)f16_policy_lma_backward_kernel<15> : (const void*)f16_policy_lma_backward_kernel<17>;
+  static uint64_t prepared[2];
+  if (int rc = policy_prepare_instance(fn, &prepared[desc->D == 17 ? 1 : 0])) return rc;
+  if (n == 0) return 0;
   a.blob = blob; a.obs = obs; a.d_mean = d_mean; a.d_values = d_values;
   a.ws = static_cast<float*>(workspace);
   a.n = n; a.row_stride = row_stride; a.frame_stride = frame_stride;
@@ -762,25 +545,14 @@ static int policy_lma_backward_impl(void* stream, const f16_policy_desc* desc, c
   a.K = m->K; a.L = m->L_new; a.C = m->C_new; a.n_layers = m->n_layers;
   a.n_pi = desc->n_pi; a.n_vf = desc->n_vf;
   a.relu = desc->activation == F16_POLICY_ACT_RELU ? 1 : 0;
-  a.nf = (int32_t)p.nf; a.act_floats = p.act_floats; a.pe_off = la.pe_off;
-  a.we = la.we;
-  a.w2 = lmab_op(la.w2_off, la.b2_off, m->C_new / 2);
-  for (int i = 0; i < m->n_layers; ++i) a.blk[i] = la.blk[i];
-  for (int i = 0; i < POL_OPS; ++i) a.ops[i] = la.ops[i];
-  const int dk = LMA_EMBED / m->heads_stacking;
+  a.nf = (int32_t)p.nf; a.act_floats = p.act_floats;
   for (int t = 0; t < m->K; ++t)
-    for (int s = 0; s < LMA_EMBED / 2; ++s) {
-      const int c = 2 * s, f = ((c / dk) * m->K + t) * dk + c % dk;
-      a.fmap[t * (LMA_EMBED / 2) + s] = (uint16_t)(f / 2);
-    }
+    for (int s = 0; s < LMA_EMBED / 2; ++s) a.fmap[t * (LMA_EMBED / 2) + s] = (uint16_t)(lma_flat_index(m, t, 2 * s) / 2);
   void* kargs[] = {&a};
   HIPCHK(hipLaunchKernel(fn, dim3((unsigned)p.grid), dim3(64), kargs, (size_t)p.lds_bytes, (hipStream_t)stream));
-  const int skip = (d_mean ? 0 : 1) | (d_values ? 0 : 2);
-  const int zero0 = (int)off[F16_POLICY_OFF_LOG_STD];
-  hipLaunchKernelGGL(f16_policy_lma_backward_reduce_kernel, dim3((unsigned)((p.nf + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, a.ws, grad_blob, (int)p.nf, p.slot_floats, p.grid, (int)off[LMAB_OFF_VF0],
-                     (int)off[F16_POLICY_OFF_ACT_W], (int)off[F16_POLICY_OFF_VAL_W], zero0,
-                     (int)off[F16_LMA_OFF_PE] + m->K * LMA_EMBED, skip);
+  // (every slot got a tile: grid <= tiles; log_std and the PE table behind it are not trained)
+  policy_launch_reduce((hipStream_t)stream, a.ws, grad_blob, p.nf, p.slot_floats, p.grid, off,
+                       off[F16_LMA_OFF_PE] + m->K * LMA_EMBED, d_mean, d_values);
   HIPCHK(hipGetLastError());
   return 0;
 }

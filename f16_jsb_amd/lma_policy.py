@@ -35,9 +35,9 @@ from .abi import (F16_LMA_BLK_ATTN_B, F16_LMA_BLK_ATTN_W, F16_LMA_BLK_FC_B, F16_
                   F16_LMA_BLK_PROJ_B, F16_LMA_BLK_PROJ_W, F16_LMA_BLOCK_SLOTS, F16_LMA_OFF_BLOCK0, F16_LMA_OFF_PE,
                   F16_LMA_OFF_W2_B, F16_LMA_OFF_W2_W, F16_LMA_OFF_WE_B, F16_LMA_OFF_WE_W, F16_POLICY_OFF_LOG_STD,
                   F16_POLICY_VALUE_ONLY, LMA_FEATURES, lma_blob_layout, lma_desc, policy_blob_layout, policy_desc)
-from .buffers import need_tensor, stream_ptr
-from .policy import (ACT_DIM, DevicePolicy, _pack_bias, _pack_weight, layers_from_state_dict, pack_blob,
-                     state_dict_from_layers, unpack_blob)
+from .buffers import need_tensor
+from .policy import (ACT_DIM, DevicePolicy, _pack_bias, _pack_weight, _unpack_weight, layers_from_state_dict,
+                     pack_blob, state_dict_from_layers, unpack_blob)
 
 NO_BACKWARD = ("the LMA backward is not built: DeviceLMAPolicy runs the rollout and predict forward only "
                "(train the extractor in torch, then load_state_dict; or opt in to the eval-mode gradient with "
@@ -181,9 +181,7 @@ def unpack_lma_blob(desc, lma, blob):
 
     def linear(what, slot_w, slot_b):
         fan_in, out = shapes[what]
-        nks = (fan_in + 1) // 2
-        w = blob[off[slot_w]:off[slot_w] + (out // 32) * nks * 64].reshape(out // 32, nks, 2, 32)
-        return w.permute(0, 3, 1, 2).reshape(out, 2 * nks)[:, :fan_in].clone(), blob[off[slot_b]:off[slot_b] + out].clone()
+        return _unpack_weight(blob, off[slot_w], fan_in, out).clone(), blob[off[slot_b]:off[slot_b] + out].clone()
     pe = blob[off[F16_LMA_OFF_PE]:off[F16_LMA_OFF_PE] + lma.K * lma.embed_dim].reshape(lma.K, lma.embed_dim).clone()
     ext = {"embed": linear("embed", F16_LMA_OFF_WE_W, F16_LMA_OFF_WE_B),
            "embed2": linear("embed2", F16_LMA_OFF_W2_W, F16_LMA_OFF_W2_B), "blocks": []}
@@ -203,23 +201,18 @@ class DeviceLMAPolicy(DevicePolicy):
     Inherits forward_into, __call__, value and predict; adds extract_features. Forward only."""
 
     def __init__(self, desc, lma, device, seed: int = 0, env_id_base: int = 0):
-        self.desc, self.lma = desc, lma
-        self.device = torch.device(device)
-        self.k, self.d = int(desc.K), int(desc.D)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.env_id_base = int(env_id_base)
-        self.calls = 0
-        self.offsets, self.n_floats = lma_blob_layout(desc, lma)
+        self.lma, self._lma_ref = lma, ctypes.byref(lma)
         self.features_dim = int(lma.L_new * lma.d_new)
-        self.blob = torch.zeros(self.n_floats, dtype=torch.float32, device=self.device)
-        self._desc_ref, self._lma_ref = ctypes.byref(desc), ctypes.byref(lma)
-        self._bwd_fns = None
-        if self.device.type == "cuda":
-            from ._lib import check, fn
-            self._fwd = fn("f16env_policy_lma_forward")
-            with torch.cuda.device(self.device):  # n = 0: prepares the kernel instance, launches nothing
-                check(self._fwd(None, self._desc_ref, self._lma_ref, None, 0, None, 0, 0, 0, 0, 0, None, None, None, None,
-                                None, 0), "f16env_policy_lma_forward")
+        super().__init__(desc, device, seed, env_id_base)
+
+    # DevicePolicy's hooks: the forward's symbol and its features_out, the second descriptor, the LMA blob
+    _FWD, _FWD_MORE = "f16env_policy_lma_forward", 1
+
+    def _desc_args(self):
+        return (self._desc_ref, self._lma_ref)
+
+    def _layout(self):
+        return lma_blob_layout(self.desc, self.lma)
 
     # ------------------------------------------------------------------------------------------
     @classmethod
@@ -269,14 +262,6 @@ class DeviceLMAPolicy(DevicePolicy):
         return sd
 
     # ------------------------------------------------------------------------------------------
-    def _launch(self, obs, n, step, eps, actions, values, log_probs, flags, features=None):
-        from ._lib import check
-        check(self._fwd(stream_ptr(self.device), self._desc_ref, self._lma_ref, self.blob.data_ptr(), n, obs.data_ptr(),
-                        obs.stride(0), obs.stride(1), self.seed, int(step) & 0xFFFFFFFFFFFFFFFF, self.env_id_base,
-                        None if eps is None else eps.data_ptr(), None if actions is None else actions.data_ptr(),
-                        values.data_ptr(), None if log_probs is None else log_probs.data_ptr(),
-                        None if features is None else features.data_ptr(), flags), "f16env_policy_lma_forward")
-
     def extract_features(self, obs, out=None):
         """The extractor's output (n, L_new * 32), what ActorCriticPolicy.extract_features returns."""
         n = self._check_obs(obs)
@@ -286,7 +271,7 @@ class DeviceLMAPolicy(DevicePolicy):
             need_tensor(out, (n, self.features_dim), torch.float32, self.device, "out", 16)
         if n:
             values = torch.empty(n, dtype=torch.float32, device=self.device)
-            self._launch(obs, n, 0, None, None, values, None, F16_POLICY_VALUE_ONLY, features=out)
+            self._launch(obs, n, 0, None, None, values, None, F16_POLICY_VALUE_ONLY, out)
         return out
 
     def forward_with_features(self, obs, step, eps=None, deterministic=False):
@@ -301,7 +286,7 @@ class DeviceLMAPolicy(DevicePolicy):
             need_tensor(eps, (n, ACT_DIM), torch.float32, self.device, "eps", 16)
         if n:
             self._launch(obs, n, step, eps, actions, values, log_probs, F16_POLICY_DETERMINISTIC if deterministic else 0,
-                         features=feats)
+                         feats)
         return actions, values, log_probs, feats
 
     # ------------------------------------------------------------------------------------------
@@ -344,11 +329,8 @@ class DeviceLMATrainPolicy(DeviceLMAPolicy):
     backward in evaluate_actions). An optimiser with weight decay would move the PE table: use none."""
 
     # DevicePolicy's own gradient entry points in place of the parent's refusals: they differ only in
-    # the two symbols and in the second descriptor (backward_blob's +0 positions include the PE table)
+    # the two symbols (backward_blob's +0 positions include the PE table)
     _BWD = ("f16env_policy_lma_backward_workspace", "f16env_policy_lma_backward")
-
-    def _desc_args(self):
-        return (self._desc_ref, self._lma_ref)
 
     parameters = DevicePolicy.parameters
     requires_grad_ = DevicePolicy.requires_grad_

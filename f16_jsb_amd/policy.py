@@ -69,6 +69,13 @@ def _pack_weight(w, fan_in, rows):
     return p.reshape(rows // 32, 32, nks, 2).permute(0, 2, 3, 1).reshape(-1)
 
 
+def _unpack_weight(blob, at, fan_in, rows):
+    """The inverse of _pack_weight for the piece at blob[at:]: W[rows][fan_in], a view (callers clone)."""
+    nks = (fan_in + 1) // 2
+    w = blob[at:at + (rows // 32) * nks * 64].reshape(rows // 32, nks, 2, 32)
+    return w.permute(0, 3, 1, 2).reshape(rows, 2 * nks)[:, :fan_in]
+
+
 def _pack_bias(b, rows):
     p = torch.zeros(rows, dtype=torch.float32, device=b.device)
     p[:b.numel()] = b.reshape(-1)
@@ -130,10 +137,8 @@ def unpack_blob(desc, blob, fan_in0=None):
         raise ValueError("a blob of %d floats was expected, got shape %s" % (total, tuple(blob.shape)))
 
     def piece(slot, rows, outs, fan_in):
-        nks = (fan_in + 1) // 2
-        w = blob[off[slot]:off[slot] + (rows // 32) * nks * 64].reshape(rows // 32, nks, 2, 32)
-        w = w.permute(0, 3, 1, 2).reshape(rows, 2 * nks)[:outs, :fan_in]
-        return w.clone(), blob[off[slot + 1]:off[slot + 1] + outs].clone()
+        bias = blob[off[slot + 1]:off[slot + 1] + outs]
+        return _unpack_weight(blob, off[slot], fan_in, rows)[:outs].clone(), bias.clone()
 
     branches = []
     for b, (widths, n) in enumerate(((desc.pi_width, desc.n_pi), (desc.vf_width, desc.n_vf))):
@@ -202,16 +207,16 @@ class DevicePolicy:
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.env_id_base = int(env_id_base)
         self.calls = 0
-        self.offsets, self.n_floats = policy_blob_layout(desc)
-        self.blob = torch.zeros(self.n_floats, dtype=torch.float32, device=self.device)
         self._desc_ref = ctypes.byref(desc)
+        self.offsets, self.n_floats = self._layout()
+        self.blob = torch.zeros(self.n_floats, dtype=torch.float32, device=self.device)
         self._bwd_fns = None
         if self.device.type == "cuda":
-            from ._lib import check, lib
-            self._fwd = lib().f16env_policy_forward
+            from ._lib import check, fn
+            self._fwd = fn(self._FWD)
             with torch.cuda.device(self.device):  # n = 0: prepares the kernel instance, launches nothing
-                check(self._fwd(None, self._desc_ref, None, 0, None, 0, 0, 0, 0, 0, None, None, None, None, 0),
-                      "f16env_policy_forward")
+                check(self._fwd(None, *self._desc_args(), None, 0, None, 0, 0, 0, 0, 0, None, None, None, None,
+                                *(None,) * self._FWD_MORE, 0), self._FWD)
 
     # ------------------------------------------------------------------------------------------
     @classmethod
@@ -249,13 +254,14 @@ class DevicePolicy:
                              % (self.k, self.d, self.device, _describe(obs)))
         return int(obs.shape[0])
 
-    def _launch(self, obs, n, step, eps, actions, values, log_probs, flags):
+    def _launch(self, obs, n, step, eps, actions, values, log_probs, flags, *more):
+        """more: the entry point's further output tensors (_FWD_MORE of them; those not given are NULL)."""
         from ._lib import check
-        check(self._fwd(stream_ptr(self.device), self._desc_ref, self.blob.data_ptr(), n, obs.data_ptr(), obs.stride(0),
-                        obs.stride(1), self.seed, int(step) & 0xFFFFFFFFFFFFFFFF, self.env_id_base,
-                        None if eps is None else eps.data_ptr(), None if actions is None else actions.data_ptr(),
-                        values.data_ptr(), None if log_probs is None else log_probs.data_ptr(), flags),
-              "f16env_policy_forward")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        more += (None,) * (self._FWD_MORE - len(more))
+        check(self._fwd(stream_ptr(self.device), *self._desc_args(), self.blob.data_ptr(), n, obs.data_ptr(), obs.stride(0),
+                        obs.stride(1), self.seed, int(step) & 0xFFFFFFFFFFFFFFFF, self.env_id_base, ptr(eps), ptr(actions),
+                        values.data_ptr(), ptr(log_probs), *map(ptr, more), flags), self._FWD)
 
     def forward_into(self, obs, step, actions, values, log_probs, eps=None, deterministic=False):
         """The forward with caller-owned outputs: actions (n, 4) 16-B aligned, values (n,),
@@ -308,12 +314,16 @@ class DevicePolicy:
         """The blob's layers under SB3's key names (model.policy.load_state_dict(pol.state_dict()))."""
         return state_dict_from_layers(*unpack_blob(self.desc, self.blob))
 
-    # the backward's two entry points and the descriptor arguments both take (an LMA policy names its
-    # own pair and adds its second descriptor)
+    # the entry points, the forward's output pointers past log_probs, the descriptor arguments all of
+    # them take and the blob's (offsets, floats): what an LMA policy replaces
+    _FWD, _FWD_MORE = "f16env_policy_forward", 0
     _BWD = ("f16env_policy_backward_workspace", "f16env_policy_backward")
 
     def _desc_args(self):
         return (self._desc_ref,)
+
+    def _layout(self):
+        return policy_blob_layout(self.desc)
 
     def _backward_fns(self):
         if self._bwd_fns is None:  # (taken at the first gradient: an older library still runs the forward)
