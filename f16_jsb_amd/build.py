@@ -4,6 +4,7 @@
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -20,11 +21,9 @@ OUT_DEBUG = os.path.join(HERE, "libf16env_debug.so")
 # and register allocation, the same rounding (-ffp-contract=on fixes contraction per source
 # expression) -- compared bit for bit against the product by tests/test_gpu_o1_differential.py
 OUT_O1 = os.path.join(HERE, "libf16env_o1.so")
-DEPS = [SRC, os.path.join(HERE, "csrc", "f16_device.h"), os.path.join(HERE, "csrc", "f16_tables.h"),
-        os.path.join(HERE, "csrc", "f16_policy.h"), os.path.join(HERE, "csrc", "f16_ppo.h"),
-        os.path.join(HERE, "csrc", "f16_ppo_am.h"), os.path.join(HERE, "csrc", "f16_policy_lma.h"),
-        os.path.join(HERE, "csrc", "f16_policy_lma_grad.h"),
-        os.path.join(ROOT, "include", "f16env.h")]
+# the one translation unit, every header beside it and the ABI header (tests/test_abi_cpu.py holds
+# this list against what the compiler reports it reads)
+DEPS = [SRC, *sorted(glob.glob(os.path.join(HERE, "csrc", "*.h"))), os.path.join(ROOT, "include", "f16env.h")]
 
 
 def hipcc() -> str:

@@ -171,7 +171,7 @@ static constexpr float PI_F = 3.14159265358979323846f;
 static constexpr double PI_D = 3.14159265358979323846;
 static constexpr float RAD2DEG_F = 57.295779513082320876798f;
 // The observation's "ordinary" angles, ANGLE_ORD_MIN <= |a| < ANGLE_ORD_END: the fp64
-// normalize_angle_mpi_pi (f16env.hip norm_angle) returns such a float32 unchanged, bit for bit
+// normalize_angle_mpi_pi (f16_env_layer.h norm_angle) returns such a float32 unchanged, bit for bit
 // (tests/test_env_layer_cpu.py walks the boundaries and pins both constants to this header).
 // Outside it: -0 and negative values below 2^-26 come back as +0 or rounded, PI_F wraps to
 // -3.1415925, NaN / Inf become 0.

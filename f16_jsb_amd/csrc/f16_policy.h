@@ -1,7 +1,7 @@
 // f16_policy.h -- the actor-critic MLP forward of a rollout as one HIP kernel (gfx950), and the
 // host side of f16env_policy_blob_layout / f16env_policy_forward (include/f16env.h, ABI 7); below
 // it the backward of the two MLPs in the blob's layout (f16env_policy_backward).
-// Included by f16env.hip after its error handling and Philox (set_err, HIPCHK, philox).
+// Needs f16_host.h (set_err, HIPCHK) and f16_rng.h (philox).
 //
 // actions, values, log_probs = policy(obs) for stable_baselines3's ActorCriticPolicy with separate
 // pi / vf MLPs (common/policies.py:ActorCriticPolicy.forward, torch_layers.py:MlpExtractor, a
@@ -22,6 +22,12 @@
 // The heads are layers of one tile (rows past 4 / 1 are zero weights); lanes 0..31 hold their
 // row's action mean in registers 0..3 and its value in register 0, and sample / store from there.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/f16env.h"
+#include "f16_host.h"
+#include "f16_rng.h"
 
 namespace f16 {
 

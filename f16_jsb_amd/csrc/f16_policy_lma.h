@@ -1,6 +1,6 @@
 // f16_policy_lma.h -- the LMA features extractor in front of the actor-critic MLPs as one HIP
 // kernel (gfx950), and the host side of f16env_policy_lma_blob_layout / f16env_policy_lma_forward
-// (include/f16env.h, ABI 7). Included by f16env.hip after f16_policy.h, whose policy_gemm /
+// (include/f16env.h, ABI 7). Needs f16_features.h (frame_features) and f16_policy.h, whose policy_gemm /
 // policy_hidden / policy_tiles / policy_sample, operand forms and C/D register map it reuses.
 // The extractor's pieces (lma_layernorm, lma_attention, lma_gelu, lma_embed_frame, lma_tile_out)
 // are written once here for this kernel and for the backward's recompute (f16_policy_lma_grad.h).
@@ -36,6 +36,8 @@
 // registers, k and v come back from the lane's own LDS slots. LayerNorm: a lane sums 16 units of
 // its row, the moments are one cross-lane add each (both lanes form a + b, the same bits).
 #pragma once
+#include "f16_features.h"
+#include "f16_policy.h"
 
 namespace f16 {
 

@@ -1,6 +1,6 @@
 // f16_policy_lma_grad.h -- the eval-mode backward of the LMA policy in the blob's own layout
 // (f16env_policy_lma_backward, include/f16env.h ABI 7), one HIP kernel plus a reduce (gfx950).
-// Included by f16env.hip after f16_policy_lma.h. It reuses, from f16_policy.h: policy_gemm, the
+// Needs f16_policy_lma.h and, through it, f16_policy.h. It reuses, from f16_policy.h: policy_gemm, the
 // whole MLP branch of f16_policy_backward_kernel (policy_bwd_branch, with policy_bwd_dw: dW^T =
 // X^T Delta and policy_bwd_db summed pairwise; the W^T Delta^T product apart as lmab_wt, one input
 // tile at a time) and the reduce kernel; from f16_policy_lma.h, at the row stride POL_XS: the
@@ -39,6 +39,7 @@
 // max_blocks) and the data alone. Rows past n - 1 carry a zero delta from the heads down (every
 // step is linear in the delta), so they add exactly nothing.
 #pragma once
+#include "f16_policy_lma.h"
 
 namespace f16 {
 

@@ -1,7 +1,7 @@
 // f16_ppo.h -- what lies between the policy's forward and its new weights in a PPO minibatch
 // update, as HIP kernels (gfx950): the loss head (f16env_ppo_loss_head) and the clipped Adam step on
-// the blob (f16env_ppo_adam_step); include/f16env.h, still ABI 7. Included by f16env.hip after
-// f16_policy.h (set_err, HIPCHK).
+// the blob (f16env_ppo_adam_step); include/f16env.h, still ABI 7. Needs f16_host.h (set_err,
+// HIPCHK).
 //
 // stable_baselines3/ppo/ppo.py:355-388 with a DiagGaussianDistribution (distributions.py): float32
 // gradients per row, the ratio and the statistics' terms in fp64 (include/f16env.h says where that
@@ -18,10 +18,15 @@
 //     element. One block, because the norm must be known before the first element moves and a blob
 //     is 26 k to 117 k floats: a second launch or a grid-wide wait would cost more than the pass.
 // No atomics, no inline assembly; the bits depend on the arguments and the data alone.
-// AM-PPO (f16_ppo_am.h, included next) shares two things defined here: the head kernel, a template
+// AM-PPO (f16_ppo_am.h, which includes this file) shares two things defined here: the head kernel, a template
 // whose <false> instance is the standard head above and whose <true> instance takes the modulated
 // advantage of ppo_am_mod, and the step's prologue (ppo_step_prologue), which the DAG step repeats.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/f16env.h"
+#include "f16_host.h"
 
 namespace f16 {
 

@@ -1,7 +1,7 @@
 // f16_ppo_am.h -- AM-PPO on the device (gfx950): the DynAGO controller over a finished rollout's
 // advantages (f16env_ppo_dynago_update), the loss head on modulated advantages
 // (f16env_ppo_loss_head_am) and the DAG / AlphaGrad step on the blob (f16env_ppo_dag_step);
-// include/f16env.h, still ABI 7. Included by f16env.hip after f16_ppo.h, whose rules hold here:
+// include/f16env.h, still ABI 7. Needs f16_ppo.h (the head kernel, ppo_step_prologue), whose rules hold here:
 // every sum in fp64 and in a fixed order, float32 results rounded once, no atomics, no inline
 // assembly, partial sums combined in the next launch's prologue.
 //
@@ -29,6 +29,7 @@
 //     per-tensor sums are taken by the 16 waves (lane l adds lanes l + 32, 16, ..., 1 by
 //     __shfl_down, fixed) and the 16 wave sums are added in wave order.
 #pragma once
+#include "f16_ppo.h"
 
 namespace f16 {
 

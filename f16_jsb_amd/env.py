@@ -434,7 +434,7 @@ class _HostWindow(_HostStaging):
     only the step's new 64-B slot block of each (position p of both device histories: 2 x N x 64
     B, contiguous) instead of the whole (N, K, 15) observation (N x K x 60 B: 39 MB per step at
     65 536 envs, K = 10). The host then repeats what the windowed step kernel does to the
-    windows of reset lanes (f16env.hip WIN block): lanes reset by this step get K-1 copies of
+    windows of reset lanes (f16_step.h step_body, WIN): lanes reset by this step get K-1 copies of
     their reset frame in the current history's window, lanes reset by the previous step get
     the same fill from the other history (the kernel's FRESH fill). The observation returned is
     a strided numpy view (N, K, 15) of the current host history's window (strides 64 B, N x 64 B,

@@ -122,7 +122,7 @@ def np_clip_actions(a):
     """np.clip(actions, action_space.low, action_space.high) (on_policy_algorithm.py:216) in
     torch with numpy's clip-ufunc semantics: min(max(x, lo), hi), max(a, b) = a if a is NaN or
     a > b else b (so NaN passes and -0 clips to +0 at a 0 bound) -- the in-kernel clip
-    (f16env.hip np_clip) computes the same."""
+    (f16_rng.h np_clip) computes the same."""
     lo = torch.tensor(ACTION_LOW, dtype=a.dtype, device=a.device)
     hi = torch.tensor(ACTION_HIGH, dtype=a.dtype, device=a.device)
     m = torch.where(torch.isnan(a) | (a > lo), a, lo)

@@ -1,6 +1,6 @@
 """Fixed workload for tests/test_gpu_env_layer.py (TEST INFRASTRUCTURE; a child process with
 F16ENV_LIB naming the library under test, and F16ENV_OCC=2 for the two-waves-per-SIMD kernels):
-the env layer's wave-uniform fast paths (f16env.hip euler_norm, env_reward_sel) must not change a
+the env layer's wave-uniform fast paths (f16_env_layer.h euler_norm, env_reward_sel) must not change a
 bit, so every library built from this source -- the product, the reference forms
 (-DF16_ENV_LAYER_REF), the -O1 and the debug builds -- must print the same sha256 per case.
 

@@ -346,3 +346,22 @@ def test_spaces_match_reference_bounds():
     act = spaces.action_space()
     np.testing.assert_array_equal(act.low, [-1, -1, -1, 0])
     np.testing.assert_array_equal(act.high, [1, 1, 1, 1])
+
+
+def test_build_deps_are_the_files_the_translation_unit_includes():
+    """build.DEPS decides when a library is stale, so it must name every project file the one
+    translation unit reads -- no more, no fewer: the compiler's own dependency list (host pass,
+    paths under the repository) equals it. And f16env.hip is the host side only: every kernel
+    is in a header of its subject (source map)."""
+    from f16_jsb_amd import build
+
+    src = os.path.join(ROOT, "f16_jsb_amd", "csrc", "f16env.hip")
+    mm = subprocess.run([build.hipcc(), "-MM", "--cuda-host-only", "-I", os.path.join(ROOT, "include"), src],
+                        capture_output=True, text=True, check=True).stdout
+    words = mm.replace("\\\n", " ").split()[1:]  # (behind the "f16env.o:" target)
+    included = {os.path.realpath(w) for w in words}
+    included = {w for w in included if w.startswith(os.path.realpath(ROOT) + os.sep)}
+    deps = {os.path.realpath(d) for d in build.DEPS}
+    assert included == deps, (sorted(included - deps), sorted(deps - included))
+    assert "__global__" not in open(src).read()
+

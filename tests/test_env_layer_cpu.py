@@ -1,4 +1,4 @@
-"""The observation's angle normalisation without fp64 on the ordinary path (f16env.hip euler_norm)
+"""The observation's angle normalisation without fp64 on the ordinary path (f16_env_layer.h euler_norm)
 against the fp64 normalize_angle_mpi_pi it replaces (norm_angle): a numpy restatement of both.
 
 The device code passes phi, theta and a non-negative psi through untouched, and gives a psi that
@@ -31,7 +31,7 @@ def bits(a):
 
 
 def norm_angle_ref(a):
-    """f16env.hip norm_angle: the fp64 form, on float32 values."""
+    """f16_env_layer.h norm_angle: the fp64 form, on float32 values."""
     a = np.asarray(a, f32)
     bad = np.isnan(a) | np.isinf(a)
     x = np.where(bad, f64(0.0), a.astype(f64))
@@ -154,7 +154,7 @@ def test_constants_are_the_headers():
     lo = re.search(r"static constexpr float ANGLE_ORD_MIN = ([0-9.eE+-]+)f;", src).group(1)
     assert f32(float(lo)) == ORD_MIN and float(lo) == 2.0 ** -24
     assert re.search(r"static constexpr float ANGLE_ORD_END = PI_F;", src)
-    env = open(os.path.join(CSRC, "f16env.hip")).read()
+    env = open(os.path.join(CSRC, "f16_env_layer.h")).read()
     # the device predicate is the one restated here, and the wrapped form the one subtraction
     assert re.search(r"m >= ANGLE_ORD_MIN && m < ANGLE_ORD_END", env)
     assert re.search(r"\(float\)\(\(double\)\(p \+ 2\.0f \* PI_F\) - 2\.0 \* PI_D\)", env)

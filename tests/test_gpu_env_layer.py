@@ -1,4 +1,4 @@
-"""Bit identity of the env layer's fast paths (f16env.hip euler_norm, env_reward_sel).
+"""Bit identity of the env layer's fast paths (f16_env_layer.h euler_norm, env_reward_sel).
 
 The one-wave-per-SIMD kernels take the observation's Euler angles through one wave-uniform test
 (no gimbal pole, every angle "ordinary": straight-line code, no fp64 normalisation) and the

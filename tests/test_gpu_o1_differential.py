@@ -1,7 +1,7 @@
 """Miscompile guard, differential.
 
 Round 3's all-zero rewards were a register-allocation miscompile of ROCm 7.2's AMDGPU backend
-in a few kernel instances (f16env.hip env_reward), found in the ISA; tests/test_isa_lint.py
+in a few kernel instances (f16_env_layer.h env_reward), found in the ISA; tests/test_isa_lint.py
 catches that bug's shape (an fp32 x - x). A recurrence of another shape would pass the lint and
 could pass the oracle tolerances if every instance miscompiled alike. Here the same source is
 built a second way -- libf16env_o1.so at -O1: other instruction selection, scheduling and

@@ -1,7 +1,7 @@
 """The kernel instances production runs use, against the CPU oracle at BASELINE sizes.
 
 VERDICT r01 "missing #2": the step kernel is a family of template instances chosen per handle
-(f16env.hip step_kernel_for): the one-wave LDS-table build for the headline (cfg3, 65 536 envs,
+(f16_step.h step_kernel_for): the one-wave LDS-table build for the headline (cfg3, 65 536 envs,
 K = 4), the two-waves-per-SIMD 256-register build for cfg5's per-GPU share (131 072 envs ->
 f16_step_var_kernel<3, 2> + f16_reset_done_kernel), the global-table build for the reference's
 stack K = 10 (f16_step_gt_kernel, jsbsim_gym.py:58), and BASELINE cfg1 (one env). Each is run
@@ -202,7 +202,7 @@ def test_cfg5_production_instance_131072(torch_mod, layout, done_list):
 def test_cfg5_inline_runic_resets_131072(torch_mod):
     """cfg5's windowed step resets a finished lane from the reset cache when it holds that
     lane's next episode (f16_ic_fill_kernel, every 64 windowed steps), and a lane that finishes
-    again within the same refill period runs its RunIC inside the step (f16env.hip step_body
+    again within the same refill period runs its RunIC inside the step (f16_step.h step_body
     in_step_reset -> lane_reset_mode). With max_steps = 5 every lane truncates every 5 steps, so
     after each lane's first (cached) reset every later reset of the 30 steps is an in-step RunIC:
     the cfg5 bench's instance f16_step_win_nt_kernel<3, 2> at 131 072 envs against the oracle --

@@ -1,7 +1,7 @@
 """Bit identity of the step kernel's counted prologue waits and windowed breakpoint counts.
 
 The product issues its state columns in first-use order and waits for each where it is first
-read (f16env.hip step_body); a -DF16_BRACKET_WINDOW build also counts the alpha / beta / Mach
+read (f16_step.h step_body); a -DF16_BRACKET_WINDOW build also counts the alpha / beta / Mach
 breakpoints over a window when every lane of a wave is inside it (f16_device.h bracket_window;
 measured no faster, so not in the product). Neither may change a result bit.
 A reference library is built from the same source with both switched off

@@ -5,7 +5,7 @@ carried a run-time reset path. Round 3 found the cause in the ISA: the shaping t
 r += 0.01 (last_d - d) of PositionReward (jsbsim_gym.py:493-507) compiled to
 `v_sub_f32 v0, v207, v207` -- the register allocator wrote the new distance into the tuple
 register that still held the previous one before reading it (a backend miscompile of ROCm 7.2's
-LLVM; the source workaround is in env_reward, f16env.hip). No fp32 source expression of the
+LLVM; the source workaround is in env_reward, f16_env_layer.h). No fp32 source expression of the
 library subtracts a value from itself, so any `v_sub_f32 vX, vY, vY` (or `v_add_f32 vX, vY, -vY`)
 in the code object is that bug again; the test disassembles every kernel and fails on one.
 

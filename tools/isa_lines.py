@@ -16,6 +16,7 @@ round 8, quotes it for the product and the -DF16_ENV_LAYER_REF forms.
 from __future__ import annotations
 
 import collections
+import glob
 import os
 import re
 import subprocess
@@ -25,7 +26,9 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "f16_jsb_amd", "csrc", "f16env.hip")
 KERNEL = "_Z22f16_step_win_nt_kernelILi0ELi1ELb0EEvPK15HIP_vector_typeIfLj4EEPKfS3_l8StepArgs"
-SOURCES = {"f16env.hip": "f16_jsb_amd/csrc/f16env.hip", "f16_device.h": "f16_jsb_amd/csrc/f16_device.h"}
+# every file under csrc/ by its base name, as the `.file` directives give it
+SOURCES = {os.path.basename(p): os.path.relpath(p, ROOT)
+           for p in glob.glob(os.path.join(ROOT, "f16_jsb_amd", "csrc", "*"))}
 
 
 def is_valu(line: str) -> bool:
