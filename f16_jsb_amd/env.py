@@ -98,6 +98,7 @@ class F16Envs:
         self.ep_return = torch.zeros(n, dtype=torch.float64, device=dev)
         self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
         self._act = torch.zeros((n, 4), dtype=f32, device=dev)
+        self._last_episode_starts = None  # (written by rollout.collect_rollout: the next rollout's episode_starts[0])
         self.fused_features, self.fused_poses = bool(fused_features), bool(fused_poses)
         self.window = obs_layout == "window"
         try:

@@ -29,6 +29,7 @@ import ctypes
 
 import torch
 
+from ._lib import check, fn
 from .abi import (F16_POLICY_DETERMINISTIC, F16_POLICY_N_OFFSETS, F16_POLICY_OFF_ACT_B, F16_POLICY_OFF_ACT_W,
                   F16_POLICY_OFF_LOG_STD, F16_POLICY_OFF_VAL_B, F16_POLICY_OFF_VAL_W, F16_POLICY_VALUE_ONLY,
                   policy_blob_layout, policy_desc)
@@ -212,7 +213,6 @@ class DevicePolicy:
         self.blob = torch.zeros(self.n_floats, dtype=torch.float32, device=self.device)
         self._bwd_fns = None
         if self.device.type == "cuda":
-            from ._lib import check, fn
             self._fwd = fn(self._FWD)
             with torch.cuda.device(self.device):  # n = 0: prepares the kernel instance, launches nothing
                 check(self._fwd(None, *self._desc_args(), None, 0, None, 0, 0, 0, 0, 0, None, None, None, None,
@@ -256,7 +256,6 @@ class DevicePolicy:
 
     def _launch(self, obs, n, step, eps, actions, values, log_probs, flags, *more):
         """more: the entry point's further output tensors (_FWD_MORE of them; those not given are NULL)."""
-        from ._lib import check
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         more += (None,) * (self._FWD_MORE - len(more))
         check(self._fwd(stream_ptr(self.device), *self._desc_args(), self.blob.data_ptr(), n, obs.data_ptr(), obs.stride(0),
@@ -327,14 +326,12 @@ class DevicePolicy:
 
     def _backward_fns(self):
         if self._bwd_fns is None:  # (taken at the first gradient: an older library still runs the forward)
-            from ._lib import fn
             self._bwd_fns = fn(self._BWD[0]), fn(self._BWD[1])
         return self._bwd_fns
 
     def reserve_backward(self, n: int, max_blocks: int = 0):
         """Size the cached workspace for gradients of up to n rows and prepare the kernel instance
         (call it ahead of a stream capture: nothing may be allocated inside one)."""
-        from ._lib import check
         ws_fn, bwd = self._backward_fns()
         need = ctypes.c_int64(0)
         check(ws_fn(*self._desc_args(), int(n), int(max_blocks), ctypes.byref(need)), self._BWD[0])
@@ -353,7 +350,6 @@ class DevicePolicy:
         """sum over rows of d_mean . d mean / d blob + d_values d value / d blob as a tensor in blob
         layout (two launches; pads and log_std slots +0). d_mean (n, 4) 16-B aligned, d_values (n,),
         contiguous float32 on the device, either may be None (that branch's gradient is zero)."""
-        from ._lib import check
         n = self._check_obs(obs)
         if obs.requires_grad:
             raise ValueError("no gradient is formed with respect to obs: pass a tensor that does not require grad")

@@ -31,6 +31,8 @@ import statistics
 
 import torch
 
+from . import _lib  # (a DevicePPO looks its entry points up as _lib.fn when it is built: tests wrap that name)
+from ._lib import F16EnvError, check
 from .abi import (F16_POLICY_OFF_LOG_STD, F16_PPO_AM_NORMALIZE, F16_PPO_DAG_FIXED_ALPHA, F16_PPO_NORMALIZE_ADV, PPO_AM_STATS,
                   PPO_DAG, PPO_DYNAGO, PPO_HYPER, PPO_STATS, policy_segments)
 from .buffers import need_tensor, stream_ptr
@@ -111,7 +113,6 @@ class DevicePPO:
     def __init__(self, pol, lr: float = 3e-4, clip_range: float = 0.2, ent_coef: float = 0.0, vf_coef: float = 0.5,
                  max_grad_norm: float = 0.5, normalize_advantage: bool = True, betas=(0.9, 0.999), eps: float = 1e-5,
                  max_batch: int = 256, max_blocks: int = 0, am_ppo=None, optimizer: str = "adam", optimizer_kwargs=None):
-        from ._lib import F16EnvError, fn
         if hasattr(pol, "lma"):  # (before anything else: the refusal needs neither a GPU nor the library)
             from .lma_policy import NO_BACKWARD
             raise NotImplementedError("DevicePPO cannot train a DeviceLMAPolicy: " + NO_BACKWARD)
@@ -122,7 +123,7 @@ class DevicePPO:
             raise ValueError("optimizer must be one of %s, got %r" % (", ".join(OPTIMIZERS), optimizer))
         if optimizer == "adam" and optimizer_kwargs:
             raise ValueError("Adam's arguments are lr, betas and eps; optimizer_kwargs is for 'dag' and 'alphagrad'")
-        self._ws_fn, self._blocks_fn, self._head, self._adam = map(fn, (
+        self._ws_fn, self._blocks_fn, self._head, self._adam = map(_lib.fn, (
             "f16env_ppo_workspace", "f16env_ppo_head_blocks", "f16env_ppo_loss_head", "f16env_ppo_adam_step"))
         self.pol, self.device = pol, pol.device
         self.normalize_advantage = bool(normalize_advantage)
@@ -143,7 +144,7 @@ class DevicePPO:
             cfg = dict(AM_PPO_DEFAULTS, **am_ppo)
             if cfg["kappa_controller"] is None:
                 cfg["kappa_controller"] = cfg["kappa"]  # (ppo.py:214)
-            self._am_head, self._dyn_ws_fn, self._dyn_update = map(fn, (
+            self._am_head, self._dyn_ws_fn, self._dyn_update = map(_lib.fn, (
                 "f16env_ppo_loss_head_am", "f16env_ppo_dynago_workspace", "f16env_ppo_dynago_update"))
             self.am_norm_adv = bool(cfg["norm_adv"])
             self.dynago, self.am_stats = z(len(PPO_DYNAGO)), z(len(PPO_AM_STATS))
@@ -151,7 +152,7 @@ class DevicePPO:
             self._dynago, self._dyn_ws, self._dyn_n = {}, torch.empty(16, dtype=torch.uint8, device=self.device), 0
             self.set_dynago(**{key: cfg[key] for key in PPO_DYNAGO})
         if optimizer != "adam":
-            self._dag_step = fn("f16env_ppo_dag_step")
+            self._dag_step = _lib.fn("f16env_ppo_dag_step")
             self._dag = _dag_constants(optimizer, optimizer_kwargs)
             self.dag = z(len(PPO_DAG))
             self.set_dag()
@@ -198,7 +199,6 @@ class DevicePPO:
         """Size the buffers and both workspaces for minibatches of up to n rows, and with AM-PPO the
         controller's workspace for `rollout` advantages (call it ahead of a stream capture: nothing
         may be allocated inside one)."""
-        from ._lib import check
         n, rollout = int(n), int(rollout)
         capturing = torch.cuda.is_current_stream_capturing()
         if self.am_ppo and rollout > self._dyn_n:
@@ -230,7 +230,6 @@ class DevicePPO:
 
     def _optimizer_step(self, grad, logstd_off, head_ws, blocks):
         """Clip + the optimiser's step on `grad`, with the head's workspace or without (None)."""
-        from ._lib import check
         pol, s = self.pol, stream_ptr(self.device)
         if self.optimizer == "adam":
             check(self._adam(s, pol.n_floats, pol.blob.data_ptr(), grad.data_ptr(), self.exp_avg.data_ptr(),
@@ -255,7 +254,6 @@ class DevicePPO:
         advantage plus old_values (ppo.py:369) and `returns` is checked and not read. Afterwards
         `grad` holds the complete gradient (before clipping) and `stats` the statistics. n == 0 does
         nothing."""
-        from ._lib import check
         if actions is None and isinstance(observations, tuple) and len(observations) == 6:
             observations, actions, old_values, old_log_prob, advantages, returns = observations
         pol = self.pol
@@ -302,7 +300,6 @@ class DevicePPO:
         train() call): any contiguous float32 device tensor, 16-B aligned, read flat. Updates
         `am_state` = (alpha, sat) on the stream; one element or none leaves it as it is. Inside a
         stream capture the workspace must have been sized by reserve(n, rollout=...)."""
-        from ._lib import check
         if not self.am_ppo:
             raise ValueError("dynago_update needs am_ppo")
         if not isinstance(advantages, torch.Tensor):

@@ -24,9 +24,11 @@ from typing import Dict, Optional
 
 import torch
 
+from ._lib import check, fn, lib
 from .abi import F16_FLAG_NO_AUTORESET, F16_OBS_DIM, F16_SLOT_CLIP, RolloutSlot, RolloutView
 from .buffers import need_tensor, stream_ptr
-from .layouts import as_act
+from .layouts import U64, as_act
+from .policy import DevicePolicy
 
 FIELDS = ("frames", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns")
 # device memory the deferred timeout bootstrap may take for its stash of terminal observations
@@ -76,8 +78,6 @@ class DeviceRolloutBuffer:
 
     def compute_returns_and_advantage(self, last_values, dones, stream=None):
         """buffers.py:403-438 on the GPU (HIP kernel f16env_gae)."""
-        from ._lib import check, lib
-
         if self.device.type != "cuda":
             raise RuntimeError("GAE runs on the GPU (f16env_gae); buffer is on %s" % self.device)
         lv = torch.as_tensor(last_values).reshape(-1).to(self.device, torch.float32).contiguous()
@@ -129,6 +129,186 @@ def np_clip_actions(a):
     return torch.where(torch.isnan(m) | (m < hi), m, hi)
 
 
+def choose_path(envs, buf, policy_fn=None, fused: bool = True, persistent: bool = True) -> str:
+    """Which way collect_rollout collects, from its arguments' attributes alone (no launch, no
+    allocation): "persistent" (one launch), "fused" (one rollout-slot launch per step) or
+    "generic" (envs.step + buf.add). Fused needs an env with step_rollout and the 16-byte
+    alignment its vector stores assume: of buf.actions and, for the contiguous layout, of
+    buf.frames[0] and the frame row; persistent also the random policy, an env with
+    rollout_random and auto-reset on."""
+    if not (fused and hasattr(envs, "step_rollout") and buf.actions.data_ptr() % 16 == 0):
+        return "generic"
+    if not getattr(envs, "window", False) and (buf.frames[0].data_ptr() % 16 or (buf.n_envs * F16_OBS_DIM * 4) % 16):
+        return "generic"
+    if persistent and policy_fn is None and hasattr(envs, "rollout_random") and not envs.cfg.flags & F16_FLAG_NO_AUTORESET:
+        return "persistent"
+    return "fused"
+
+
+def slot_cursor(buf, carry, window: bool, seed: int, step0: int, clip: bool):
+    """(slot, move): the RolloutSlot of a fused rollout and move(t) -> slot, which points its rows
+    at step t by integer arithmetic on addresses and row strides taken here, once (the buffer
+    was allocated with these shapes: no per-step views or checks on the launch path). The
+    contiguous layout writes frames[t], the windowed one frames[t + 1] (the returned
+    observation's newest frame; the last step none); next_start is episode_starts[t + 1], the
+    last step's `carry`. No GPU call."""
+    n, T, step0 = buf.n_envs, buf.n_steps, int(step0)
+    slot = RolloutSlot(int(seed) & U64, 0, None, None, None, None, None, None, F16_SLOT_CLIP if clip else 0, 0)
+    fr0, ac0, rw0, st0 = (x.data_ptr() for x in (buf.frames, buf.actions, buf.rewards, buf.episode_starts))
+    fb, ab, rb, last = n * F16_OBS_DIM * 4, n * 16, n * 4, carry.data_ptr()
+
+    def move(t):
+        slot.act_step = (step0 + t) & U64
+        if window:
+            slot.next_frame = fr0 + (t + 1) * fb if t + 1 < T else None
+        else:
+            slot.frame = fr0 + t * fb
+        slot.actions, slot.rewards = ac0 + t * ab, rw0 + t * rb
+        slot.next_start = st0 + (t + 1) * rb if t + 1 < T else last
+        return slot
+    return slot, move
+
+
+def stash_capacity(n: int, T: int, max_steps: int) -> int:
+    """Rows the deferred bootstrap's stash needs: a lane truncates at most once per max_steps
+    steps (auto-reset restarts its counter), so at most (T - 1) // max_steps + 1 times in T."""
+    return n * ((T - 1) // max(1, int(max_steps)) + 1)
+
+
+def can_defer(envs, buf, policy_fn, bootstrap: str) -> bool:
+    """Whether the timeout bootstrap is deferred: asked for, with a policy, on an auto-resetting
+    handle, and the stash within STASH_MAX_BYTES (very short TimeLimits: else per step)."""
+    return policy_fn is not None and bootstrap == "deferred" and not int(envs.cfg.flags) & F16_FLAG_NO_AUTORESET \
+        and stash_capacity(buf.n_envs, buf.n_steps, envs.cfg.max_steps) * buf.k * F16_OBS_DIM * 4 <= STASH_MAX_BYTES
+
+
+class _DeferredBootstrap:
+    """The stash of the truncated lanes' terminal observations: push after each step
+    (f16env_bootstrap_stash, no host sync), apply once after the loop."""
+
+    def __init__(self, envs, buf):
+        dev, self.n, self.k, self.gamma = buf.device, buf.n_envs, buf.k, buf.gamma
+        self.cap = stash_capacity(buf.n_envs, buf.n_steps, envs.cfg.max_steps)
+        self.stash = torch.empty((self.cap, buf.k, F16_OBS_DIM), dtype=torch.float32, device=dev)
+        self.idx = torch.empty(self.cap, dtype=torch.int64, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.dev, self.fn = dev, lib().f16env_bootstrap_stash
+        self.ptrs = (self.stash.data_ptr(), self.idx.data_ptr(), self.count.data_ptr(), self.cap)
+
+    def push(self, out, t):
+        tobs, n = out.terminal_obs, self.n
+        check(self.fn(stream_ptr(self.dev), n, self.k, tobs.data_ptr(), tobs.stride(0), tobs.stride(1),
+                      out.terminated.data_ptr(), out.truncated.data_ptr(), t * n, *self.ptrs), "f16env_bootstrap_stash")
+
+    def apply(self, vfn, rewards):
+        """V once over every stashed terminal observation, then rewards += gamma * V."""
+        m = int(self.count.item())
+        if m > self.cap:
+            raise RuntimeError("bootstrap stash overflow (%d > %d)" % (m, self.cap))
+        if m:
+            tv = vfn(self.stash[:m]).reshape(-1).to(torch.float32).contiguous()
+            check(lib().f16env_bootstrap_apply(stream_ptr(self.dev), m, rewards.data_ptr(), self.idx.data_ptr(),
+                                               tv.data_ptr(), self.gamma), "f16env_bootstrap_apply")
+
+
+class _NoBootstrap:
+    """The same two calls for the random policy, which has no value function: nothing bootstraps."""
+
+    def push(self, out, t):
+        pass
+
+    def apply(self, vfn, rewards):
+        pass
+
+
+class _PerStepBootstrap(_NoBootstrap):
+    """V over the step's whole batch of terminal observations every step
+    (f16env_bootstrap_timeouts): nothing is left to apply."""
+
+    def __init__(self, buf, vfn):
+        self.dev, self.n, self.gamma, self.vfn = buf.device, buf.n_envs, buf.gamma, vfn
+        self.rw0, self.fn = buf.rewards.data_ptr(), lib().f16env_bootstrap_timeouts
+
+    def push(self, out, t):
+        tv = self.vfn(out.terminal_obs).reshape(-1).to(torch.float32).contiguous()
+        check(self.fn(stream_ptr(self.dev), self.n, self.rw0 + t * self.n * 4, out.terminated.data_ptr(),
+                      out.truncated.data_ptr(), tv.data_ptr(), self.gamma), "f16env_bootstrap_timeouts")
+
+
+def _policy_adaptor(envs, buf, policy_fn, step0: int):
+    """act(obs, t) -> the address of step t's (N, 4) actions, values[t] and log_probs[t] written:
+    None for the random policy (the step kernel draws them); a DevicePolicy writes the buffer's
+    rows itself and its actions into one reused scratch (no per-step copies or shape fix-ups);
+    a closure's results are copied in."""
+    n, values, log_probs = buf.n_envs, buf.values, buf.log_probs
+    if policy_fn is None:
+        return lambda obs, t: None
+    if isinstance(policy_fn, DevicePolicy):
+        scratch = torch.empty((n, 4), dtype=torch.float32, device=buf.device)
+        forward_into, step0, ptr = policy_fn.forward_into, int(step0), scratch.data_ptr()
+
+        def act(obs, t):
+            forward_into(obs, step0 + t, scratch, values[t], log_probs[t])
+            return ptr
+        return act
+    held = [None]  # (the actions stay alive until the next step's replace them)
+
+    def act(obs, t):
+        a, v, lp = policy_fn(obs)
+        held[0] = a = as_act(envs, a.reshape(n, 4), "policy actions")
+        values[t].copy_(v.reshape(-1))
+        log_probs[t].copy_(lp.reshape(-1))
+        return a.data_ptr()
+    return act
+
+
+def _collect_persistent(envs, buf, seed, step0, carry):
+    """The whole rollout in one launch (random policy); returns the final observation."""
+    envs.rollout_random(seed, step0, buf.n_steps, buf.frames, buf.actions, buf.rewards,
+                        buf.episode_starts[1:] if buf.n_steps > 1 else None, carry)
+    return envs.obs
+
+
+def _collect_fused(envs, buf, seed, step0, policy_fn, vfn, bootstrap, carry):
+    """One rollout-slot launch per step; per step: the slot's addresses, at most one policy
+    call, the launch, at most one bootstrap call. Returns the final observation."""
+    obs, window = envs.obs, bool(getattr(envs, "window", False))
+    if window:  # the log's first frame; step t then writes frames[t + 1] (the returned obs's newest)
+        buf.frames[0].copy_(obs[:, -1])
+    move = slot_cursor(buf, carry, window, seed, step0, clip=policy_fn is not None)[1]
+    act = _policy_adaptor(envs, buf, policy_fn, step0)
+    boot = _NoBootstrap() if policy_fn is None else _DeferredBootstrap(envs, buf) \
+        if can_defer(envs, buf, policy_fn, bootstrap) else _PerStepBootstrap(buf, vfn)
+    step, push = envs._step_rollout_raw, boot.push
+    for t in range(buf.n_steps):
+        out = step(move(t), act(obs, t))
+        push(out, t)
+        obs = out.obs
+    boot.apply(vfn, buf.rewards)
+    return obs
+
+
+def _collect_generic(envs, buf, seed, step0, policy_fn, vfn, starts, zeros):
+    """envs.step + buf.add per step (any env with obs / step / sample_actions); returns the
+    final observation and the episode starts after the last step."""
+    obs = envs.obs
+    for t in range(buf.n_steps):
+        obs = obs.clone()  # (an env may reuse its observation buffer in the step below)
+        if policy_fn is not None:
+            act, v, lp = policy_fn(obs)
+            act = act.reshape(buf.n_envs, -1).to(torch.float32)
+            out = envs.step(np_clip_actions(act).contiguous())
+            rew = bootstrap_timeouts(out.rew, out.terminated, out.truncated, vfn(out.terminal_obs), buf.gamma)
+        else:
+            act, v, lp = envs.sample_actions(seed, step0 + t), zeros, zeros
+            out = envs.step(act)
+            rew = out.rew
+        buf.add(obs, act, rew, starts, v, lp)
+        obs = out.obs
+        starts = (out.terminated | out.truncated).to(torch.float32)
+    return obs, starts
+
+
 def collect_rollout(envs, buf: DeviceRolloutBuffer, seed: int = 0, step0: int = 0, policy_fn=None, value_fn=None,
                     fused: bool = True, persistent: bool = True, bootstrap: str = "deferred"):
     """collect_rollouts (on_policy_algorithm.py:162-268) over device tensors. Starts from the
@@ -167,142 +347,35 @@ def collect_rollout(envs, buf: DeviceRolloutBuffer, seed: int = 0, step0: int = 
     :236-245); both modes here evaluate a batch, so for a value head whose GEMMs round a row
     differently at another batch size the bootstrapped rewards may differ from SB3's, and between
     the two modes, in the last bits (tests/test_gpu_policy_rollout.py
-    test_bootstrap_modes_vs_batch_of_one bounds it); the lanes that bootstrap are the same."""
-
-    dev = buf.device
-    n = buf.n_envs
-    T = buf.n_steps
+    test_bootstrap_modes_vs_batch_of_one bounds it); the lanes that bootstrap are the same.
+    Any other `bootstrap`, on every path, and a fused rollout whose buffer and envs sit on
+    different devices raise ValueError before anything is written."""
+    if bootstrap not in ("deferred", "per_step"):
+        raise ValueError("bootstrap must be 'deferred' or 'per_step'")
+    path = choose_path(envs, buf, policy_fn, fused, persistent)
+    dev, n = buf.device, buf.n_envs
+    if path == "fused" and getattr(envs, "device", dev) != dev:
+        raise ValueError("rollout buffer on %s, envs on %s" % (dev, envs.device))
+    vfn = value_fn if value_fn is not None else policy_fn.value if isinstance(policy_fn, DevicePolicy) \
+        else (lambda o: policy_fn(o)[1])
     zeros = torch.zeros(n, dtype=torch.float32, device=dev)
-    obs = envs.obs
     starts = getattr(envs, "_last_episode_starts", None)
     if starts is None:
         starts = torch.ones(n, dtype=torch.float32, device=dev)
     buf.reset()
-    window = bool(getattr(envs, "window", False))
-    from .policy import DevicePolicy
-    device_policy = isinstance(policy_fn, DevicePolicy)
-    if device_policy and value_fn is None:
-        value_fn = policy_fn.value
-    vfn = value_fn if value_fn is not None else (lambda o: policy_fn(o)[1])
-    use_fused = fused and hasattr(envs, "step_rollout") and buf.actions.data_ptr() % 16 == 0 \
-        and (window or (buf.frames[0].data_ptr() % 16 == 0 and (n * F16_OBS_DIM * 4) % 16 == 0))
-    use_persistent = use_fused and persistent and policy_fn is None and hasattr(envs, "rollout_random") \
-        and not (envs.cfg.flags & F16_FLAG_NO_AUTORESET)
-    last_v = zeros
-    if use_persistent:
-        carry = torch.empty(n, dtype=torch.float32, device=dev)
-        buf.obs0.copy_(obs)
-        buf.episode_starts[0].copy_(starts)
-        envs.rollout_random(seed, step0, T, buf.frames, buf.actions, buf.rewards,
-                            buf.episode_starts[1:] if T > 1 else None, carry)
-        obs = envs.obs
-        buf.pos = T
-        starts = carry
-    elif use_fused:
-        from ._lib import check, lib
-        carry = torch.empty(n, dtype=torch.float32, device=dev)
-        buf.obs0.copy_(obs)
-        buf.episode_starts[0].copy_(starts)
-        if window:  # the log's first frame; step t then writes frames[t + 1] (the returned obs's newest)
-            buf.frames[0].copy_(obs[:, -1])
-        # the slot is built once and its row addresses moved per step (the buffer was allocated
-        # with these shapes on this device: no per-step checks on the launch path)
-        if getattr(envs, "device", dev) != dev:
-            raise ValueError("rollout buffer on %s, envs on %s" % (dev, envs.device))
-        raw = hasattr(envs, "_step_rollout_raw")
-        slot = RolloutSlot(int(seed) & 0xFFFFFFFFFFFFFFFF, 0, None, None, None, None, None, None,
-                           F16_SLOT_CLIP if policy_fn is not None else 0, 0)
-        fr0, ac0, rw0, st0 = (buf.frames.data_ptr(), buf.actions.data_ptr(), buf.rewards.data_ptr(),
-                              buf.episode_starts.data_ptr())
-        fb, ab, rb = n * F16_OBS_DIM * 4, n * 16, n * 4
-        L = lib()
-        boot = L.f16env_bootstrap_timeouts
-        defer = policy_fn is not None and bootstrap == "deferred" \
-            and not (int(getattr(envs, "cfg").flags) & F16_FLAG_NO_AUTORESET)
-        if bootstrap not in ("deferred", "per_step"):
-            raise ValueError("bootstrap must be 'deferred' or 'per_step'")
-        # a lane truncates at most once per max_steps steps (auto-reset restarts its counter),
-        # so it enters the stash at most (T - 1) // max_steps + 1 times in T steps; a stash that
-        # would pass STASH_MAX_BYTES (very short TimeLimits) falls back to the per-step bootstrap
-        cap = n * ((T - 1) // max(1, int(envs.cfg.max_steps)) + 1)
-        defer = defer and cap * buf.k * F16_OBS_DIM * 4 <= STASH_MAX_BYTES
-        if defer:
-            stash = torch.empty((cap, buf.k, F16_OBS_DIM), dtype=torch.float32, device=dev)
-            stash_idx = torch.empty(cap, dtype=torch.int64, device=dev)
-            stash_n = torch.zeros(1, dtype=torch.int32, device=dev)
-            stash_fn = L.f16env_bootstrap_stash
-        # a DevicePolicy writes values / log-probs straight into the buffer's rows and its actions
-        # into one reused scratch the step's slot reads: no per-step copies or shape fix-ups
-        device_policy = device_policy and raw
-        if device_policy:
-            act_scratch = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        for t in range(T):
-            act_ptr = None
-            if device_policy:
-                policy_fn.forward_into(obs, int(step0) + t, act_scratch, buf.values[t], buf.log_probs[t])
-                act_ptr = act_scratch.data_ptr()
-            elif policy_fn is not None:
-                act, v, lp = policy_fn(obs)
-                act = as_act(envs, act.reshape(n, 4), "policy actions")
-                act_ptr = act.data_ptr()
-                buf.values[t].copy_(v.reshape(-1))
-                buf.log_probs[t].copy_(lp.reshape(-1))
-            if raw:
-                slot.act_step = (int(step0) + t) & 0xFFFFFFFFFFFFFFFF
-                if window:
-                    slot.next_frame = fr0 + (t + 1) * fb if t + 1 < T else None
-                else:
-                    slot.frame = fr0 + t * fb
-                slot.actions, slot.rewards = ac0 + t * ab, rw0 + t * rb
-                slot.next_start = st0 + (t + 1) * rb if t + 1 < T else carry.data_ptr()
-                out = envs._step_rollout_raw(slot, act_ptr)
-            else:
-                nxt = buf.episode_starts[t + 1] if t + 1 < T else carry
-                frame_kw = ({"next_frame": buf.frames[t + 1] if t + 1 < T else None} if window
-                            else {"frame": buf.frames[t]})
-                out = envs.step_rollout(seed, step0 + t, actions=buf.actions[t], rewards=buf.rewards[t],
-                                        next_start=nxt, policy_actions=act if policy_fn is not None else None,
-                                        clip=policy_fn is not None, **frame_kw)
-            if defer:  # the truncated lanes' terminal observations into the stash
-                tobs = out.terminal_obs
-                check(stash_fn(stream_ptr(dev), n, buf.k, tobs.data_ptr(), tobs.stride(0), tobs.stride(1),
-                               out.terminated.data_ptr(), out.truncated.data_ptr(), t * n, stash.data_ptr(),
-                               stash_idx.data_ptr(), stash_n.data_ptr(), cap), "f16env_bootstrap_stash")
-            elif policy_fn is not None:  # timeout bootstrap on the step's terminal observations
-                tv = vfn(out.terminal_obs).reshape(-1).to(torch.float32).contiguous()
-                check(boot(stream_ptr(dev), n, rw0 + t * rb, out.terminated.data_ptr(), out.truncated.data_ptr(),
-                           tv.data_ptr(), buf.gamma), "f16env_bootstrap_timeouts")
-            obs = out.obs
-        if defer:  # V once over every stashed terminal observation, then rewards += gamma * V
-            m = int(stash_n.item())
-            if m > cap:
-                raise RuntimeError("bootstrap stash overflow (%d > %d)" % (m, cap))
-            if m:
-                tv = vfn(stash[:m]).reshape(-1).to(torch.float32).contiguous()
-                check(L.f16env_bootstrap_apply(stream_ptr(dev), m, rw0, stash_idx.data_ptr(), tv.data_ptr(), buf.gamma),
-                      "f16env_bootstrap_apply")
-        buf.pos = T
-        starts = carry
+    if path == "generic":  # (buf.add keeps obs0 and episode_starts[0] itself)
+        obs, starts = _collect_generic(envs, buf, seed, step0, policy_fn, vfn, starts, zeros)
     else:
-        for t in range(T):
-            obs = obs.clone()  # (an env may reuse its observation buffer in the step below)
-            if policy_fn is not None:
-                act, v, lp = policy_fn(obs)
-                act = act.reshape(n, -1).to(torch.float32)
-                out = envs.step(np_clip_actions(act).contiguous())
-            else:
-                act, v, lp = envs.sample_actions(seed, step0 + t), zeros, zeros
-                out = envs.step(act)
-            rew = out.rew
-            if policy_fn is not None:
-                rew = bootstrap_timeouts(rew, out.terminated, out.truncated, vfn(out.terminal_obs), buf.gamma)
-            buf.add(obs, act, rew, starts, v, lp)
-            obs = out.obs
-            starts = (out.terminated | out.truncated).to(torch.float32)
+        buf.obs0.copy_(envs.obs)
+        buf.episode_starts[0].copy_(starts)
+        starts = torch.empty(n, dtype=torch.float32, device=dev)  # the carry: the episode starts after the last step
+        if path == "persistent":
+            obs = _collect_persistent(envs, buf, seed, step0, starts)
+        else:
+            obs = _collect_fused(envs, buf, seed, step0, policy_fn, vfn, bootstrap, starts)
+        buf.pos = buf.n_steps
     envs._last_episode_starts = starts
-    if policy_fn is not None:
-        last_v = vfn(obs).reshape(-1).to(torch.float32)
-    return last_v, starts
+    return (vfn(obs).reshape(-1).to(torch.float32) if policy_fn is not None else zeros), starts
 
 
 def bootstrap_timeouts(rewards, terminated, truncated, terminal_values, gamma: float):
@@ -455,8 +528,6 @@ def rollout_minibatch(src, indices, k: Optional[int] = None, out: Optional[Rollo
     yields a row of NaN (DeviceRolloutBuffer.get range-checks its caller's indices instead).
     out: caller-owned RolloutSamples to write into. With `out` given the call allocates nothing and
     never synchronises, so it can be captured in a HIP graph."""
-    from ._lib import check, fn
-
     v = src if isinstance(src, _View) else _View(src, k)
     batch = indices.numel() if isinstance(indices, torch.Tensor) else 0
     need_tensor(indices, (batch,), torch.int64, v.device, "indices", 8)
