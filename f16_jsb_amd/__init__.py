@@ -18,9 +18,12 @@ ENV_ID = "JSBSim-v0"
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
-    if name in ("F16Envs", "F16VecEnv", "F16GymVectorEnv", "F16GymEnv", "reference_goal", "StepOut"):
+    if name in ("F16Envs", "reference_goal", "StepOut"):
         from . import env
         return getattr(env, name)
+    if name in ("F16VecEnv", "F16GymVectorEnv", "F16GymEnv"):
+        from . import vec_env
+        return getattr(vec_env, name)
     if name == "DevicePolicy":
         from .policy import DevicePolicy
         return DevicePolicy
@@ -40,7 +43,7 @@ def make(env_id: str = ENV_ID, num_envs: int = 1, **kw):
     SB3 is importable, so base_class.py:215 does not re-wrap it."""
     if env_id != ENV_ID:
         raise KeyError("unknown env id %r (only %r)" % (env_id, ENV_ID))
-    from .env import F16VecEnv
+    from .vec_env import F16VecEnv
     return F16VecEnv(num_envs=num_envs, **kw)
 
 
@@ -49,7 +52,7 @@ def make_vec(env_id: str = ENV_ID, num_envs: int = 1, **kw):
     (F16GymVectorEnv, autoreset SAME_STEP) over the same kernel."""
     if env_id != ENV_ID:
         raise KeyError("unknown env id %r (only %r)" % (env_id, ENV_ID))
-    from .env import F16GymVectorEnv
+    from .vec_env import F16GymVectorEnv
     return F16GymVectorEnv(num_envs=num_envs, **kw)
 
 
@@ -65,9 +68,9 @@ def register_gymnasium() -> bool:
     registry = getattr(gymnasium, "registry", getattr(getattr(gymnasium, "envs", None), "registry", {}))
     if ENV_ID in registry:
         return False
-    kw = dict(id=ENV_ID, entry_point="f16_jsb_amd.env:make_gym_env", max_episode_steps=1200)
+    kw = dict(id=ENV_ID, entry_point="f16_jsb_amd.vec_env:make_gym_env", max_episode_steps=1200)
     try:
-        gymnasium.register(vector_entry_point="f16_jsb_amd.env:make_gym_vector_env", **kw)
+        gymnasium.register(vector_entry_point="f16_jsb_amd.vec_env:make_gym_vector_env", **kw)
     except TypeError:  # gymnasium < 1.0: no vector entry points
         gymnasium.register(**kw)
     return True

@@ -21,6 +21,18 @@ def need_tensor(x, shape, dtype, device, name, align: int = 4, optional: bool = 
                          % (name, align, str(dtype).replace("torch.", ""), tuple(shape), device))
 
 
+def step_flags_bytes(n: int) -> int:
+    """Size of the packed per-step outputs of n envs: rewards (f32), terminated, truncated (u8) in
+    one uint8 buffer, padded to 16 bytes, so that a host-side consumer moves the three in one copy."""
+    return (6 * n + 15) // 16 * 16
+
+
+def split_step_flags(buf, n: int, f32):
+    """(rew, term, trunc) views of a packed step_flags buffer of n envs; `buf` is a uint8 torch tensor
+    or numpy array, `f32` its library's float32."""
+    return buf[:4 * n].view(f32), buf[4 * n:5 * n], buf[5 * n:6 * n]
+
+
 def stream_ptr(device) -> ctypes.c_void_p:
     """The caller's current stream on `device`, as the ABI's `void* stream`."""
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)

@@ -1,30 +1,25 @@
-"""Host side of the MI355X F-16 environment.
+"""Host side of the MI355X F-16 environment: the handle.
 
 ``F16Envs``   -- thin owner of one libf16env handle: device tensors in, device tensors out
                  (the throughput path; no per-step allocation, no host sync); what depends on
                  the observation layout is in layouts.py.
-``F16VecEnv`` -- drop-in for the reference's VecEnv boundary
-                 (stable_baselines3/common/vec_env/base_vec_env.py:50-357 VecEnv ABC,
-                 dummy_vec_env.py:56-83 auto-reset / info contract, monitor.py:85-111
-                 episode stats) over ``F16Envs``, returning numpy like DummyVecEnv.
 ``reference_goal`` -- jsbsim_gym.py:312-323 with numpy's default_rng(seed), used for
                  seeded resets so seeded goals match the reference bit for bit.
+The drop-in facades over a handle (F16VecEnv, F16GymVectorEnv, F16GymEnv) are in vec_env.py, the
+host staging of their numpy mode in host_staging.py; the three class names still resolve here.
 """
 from __future__ import annotations
 
 import ctypes
-import time
-from copy import deepcopy
 from functools import partial
-from typing import Any, Optional, Sequence
+from typing import Optional
 
 import numpy as np
 
-from . import spaces
 from ._lib import F16EnvError, check, lib
 from .abi import (RolloutSlot, F16C_N, F16_IC_N, F16_OBS_DIM, F16_FLAG_NAN_GUARD, F16_FLAG_NO_AUTORESET,
                   F16_FLAG_OBS_CHECK, F16_SLOT_CLIP, EnvConfig, algorithmic_bytes_per_env_step, config_default)
-from .buffers import need_tensor
+from .buffers import need_tensor, split_step_flags, step_flags_bytes
 from .layouts import U64, StepOut, _ContiguousLayout, _default_history, _ptr, _WindowLayout, as_act  # noqa: F401
 
 
@@ -91,16 +86,16 @@ class F16Envs:
         f32, dev = torch.float32, self.device
         # rewards (f32), terminated, truncated (u8) in ONE allocation, so a host-side consumer
         # (F16VecEnv's numpy mode) moves the three with a single device-to-host copy
-        nb = (4 * n + 2 * n + 15) // 16 * 16
-        self.step_flags = torch.zeros(nb, dtype=torch.uint8, device=dev)
-        self.rew = self.step_flags[:4 * n].view(f32)
-        self.term, self.trunc = self.step_flags[4 * n:5 * n], self.step_flags[5 * n:6 * n]
+        self.step_flags = torch.zeros(step_flags_bytes(n), dtype=torch.uint8, device=dev)
+        self.rew, self.term, self.trunc = split_step_flags(self.step_flags, n, f32)
         self.ep_return = torch.zeros(n, dtype=torch.float64, device=dev)
         self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
         self._act = torch.zeros((n, 4), dtype=f32, device=dev)
         self._last_episode_starts = None  # (written by rollout.collect_rollout: the next rollout's episode_starts[0])
         self.fused_features, self.fused_poses = bool(fused_features), bool(fused_poses)
         self.window = obs_layout == "window"
+        # a host mirror can follow this handle one frame slot per step (host_staging._HostWindow)
+        self.mirrors_by_slot = self.window and window_order == "position"
         try:
             if obs_layout not in ("contiguous", "window"):
                 raise ValueError("obs_layout must be 'contiguous' or 'window'")
@@ -118,6 +113,11 @@ class F16Envs:
 
     obs = property(lambda self: self._layout.obs)
     terminal_obs = property(lambda self: self._layout.terminal_obs)  # (windowed: the other history's window)
+
+    def new_frame_slots(self):
+        """Windowed layout: the last step's two new (N, 16) slot blocks, of the current and of the
+        other history."""
+        return self._layout.new_slots()
 
     def close(self):
         h = getattr(self, "_h", None)
@@ -335,547 +335,8 @@ class F16Envs:
         return out
 
 
-def _optional_class(module: str, name: str):
-    """A base class from an optional dependency (stable_baselines3 / gymnasium), or None."""
-    try:
-        mod = __import__(module, fromlist=[name])
-        return getattr(mod, name)
-    except Exception:  # noqa: BLE001 - absent or broken: the duck-typed surface is used
-        return None
-
-
-# stable_baselines3/common/base_class.py:215 accepts an env as-is only when
-# isinstance(env, VecEnv); gymnasium learners check gymnasium.Env / gymnasium.vector.VectorEnv.
-# When those libraries are importable the facades below ARE subclasses of their ABCs.
-SB3VecEnv = _optional_class("stable_baselines3.common.vec_env.base_vec_env", "VecEnv")
-GymEnv = _optional_class("gymnasium", "Env")
-GymVectorEnv = _optional_class("gymnasium.vector", "VectorEnv")
-
-
-def _bases(*classes):
-    return tuple(c for c in classes if c is not None) or (object,)
-
-
-class _ReadOnlyInfo(dict):
-    """The info dict of every lane that did not finish its step: {"TimeLimit.truncated": False}
-    (dummy_vec_env.py:56-73 through TimeLimit + Monitor). ONE shared, immutable instance per
-    step instead of N fresh dicts; lanes that finished get fresh dicts of their own."""
-
-    def _ro(self, *a, **k):
-        raise TypeError("info of a lane that did not finish is shared and read-only")
-
-    __setitem__ = __delitem__ = update = pop = popitem = clear = setdefault = _ro  # type: ignore[assignment]
-
-    def copy(self):
-        return dict(self)
-
-    def __deepcopy__(self, memo):
-        return dict(self)
-
-
-_NOT_DONE_INFO = _ReadOnlyInfo({"TimeLimit.truncated": False})
-
-
-class _HostStaging:
-    """Numpy mode of the facades: pinned host buffers the step's outputs land in, with one
-    stream sync per step. obs goes to a ring of `ring` pinned (N, K, 15) buffers -- the arrays a
-    step returns stay valid for `ring` - 1 further steps (SB3 copies obs into its buffers one step
-    later: on_policy_algorithm.py:250-257, off_policy_algorithm.py _store_transition); rewards /
-    terminated / truncated arrive by ONE copy of the handle's packed step_flags buffer."""
-
-    def __init__(self, envs: "F16Envs", ring: int = 3):
-        t = envs.torch
-        self.t, self.envs = t, envs
-        pin = envs.device.type == "cuda"
-        n, k = envs.n, envs.k
-        self.obs = [t.empty((n, k, F16_OBS_DIM), dtype=t.float32, pin_memory=pin) for _ in range(ring)]
-        self.flags = t.empty(envs.step_flags.shape, dtype=t.uint8, pin_memory=pin)
-        self.act = t.empty((n, 4), dtype=t.float32, pin_memory=pin)
-        self.i = 0
-
-    def actions_to_device(self, actions):
-        """Host actions -> the handle's device action buffer through pinned staging; tensors on
-        the device go through as_act (aligned float32 (N, 4) ones untouched)."""
-        t, e = self.t, self.envs
-        if isinstance(actions, t.Tensor):
-            if actions.device == e.device and actions.numel() == e.n * 4:
-                return as_act(e, actions.reshape(e.n, 4))
-            actions = actions.detach().to("cpu", t.float32).numpy()
-        a = np.asarray(actions, dtype=np.float32)
-        if a.size != e.n * 4:
-            raise ValueError("actions must hold (N, 4) = (%d, 4) values, got shape %s" % (e.n, a.shape))
-        self.act.numpy()[...] = a.reshape(e.n, 4)
-        e._act.copy_(self.act, non_blocking=True)
-        return e._act
-
-    def fetch(self, obs_dev, with_flags: bool = True):
-        """Copy obs (and rew/term/trunc) to pinned memory, wait once; numpy views."""
-        o = self.obs[self.i]
-        self.i = (self.i + 1) % len(self.obs)
-        o.copy_(obs_dev, non_blocking=True)
-        if with_flags:
-            self.flags.copy_(self.envs.step_flags, non_blocking=True)
-        if self.envs.device.type == "cuda":
-            self.t.cuda.current_stream(self.envs.device).synchronize()
-        n = self.envs.n
-        f = self.flags.numpy()
-        return o.numpy(), f[:4 * n].view(np.float32), f[4 * n:5 * n], f[5 * n:6 * n]
-
-    def done_rows(self, idx: np.ndarray):
-        """terminal obs, episode return / length of the lanes in idx (small device gathers)."""
-        e, t = self.envs, self.t
-        i = t.as_tensor(idx, dtype=t.int64).to(e.device, non_blocking=True)
-        return (e.terminal_obs.index_select(0, i).cpu().numpy(), e.ep_return.index_select(0, i).cpu().numpy(),
-                e.ep_len.index_select(0, i).cpu().numpy())
-
-
-class _HostWindow(_HostStaging):
-    """Numpy mode over a windowed handle (obs_layout="window", position-major): the host keeps
-    a pinned mirror of the device's two frame histories, [2][Th][N][16], and per step copies
-    only the step's new 64-B slot block of each (position p of both device histories: 2 x N x 64
-    B, contiguous) instead of the whole (N, K, 15) observation (N x K x 60 B: 39 MB per step at
-    65 536 envs, K = 10). The host then repeats what the windowed step kernel does to the
-    windows of reset lanes (f16_step.h step_body, WIN): lanes reset by this step get K-1 copies of
-    their reset frame in the current history's window, lanes reset by the previous step get
-    the same fill from the other history (the kernel's FRESH fill). The observation returned is
-    a strided numpy view (N, K, 15) of the current host history's window (strides 64 B, N x 64 B,
-    4 B), valid until the step after next -- the device layout's guarantee, which SB3 needs
-    (it stores obs one step later, on_policy_algorithm.py:247-254); the terminal observation is
-    the other history's window, as on the device. The host ring has its own Th positions and
-    moves its last K-1 to the front when full."""
-
-    def __init__(self, envs: "F16Envs", th: int = 0):
-        super().__init__(envs, ring=0)  # (the pinned flags and action staging; no observation ring)
-        self.Th = int(th) if th else max(128, 4 * envs.k)
-        self.H = self.t.zeros((2, self.Th, envs.n, 16), dtype=self.t.float32, pin_memory=envs.device.type == "cuda")
-        self.Hn = self.H.numpy()
-        self.par, self.q, self.prev_reset = 0, envs.k - 1, None
-        self.autoreset = not (int(envs.cfg.flags) & F16_FLAG_NO_AUTORESET)
-
-    def _view(self, par: int) -> np.ndarray:
-        k, q = self.envs.k, self.q
-        return self.Hn[par, q - k + 1:q + 1, :, :F16_OBS_DIM].transpose(1, 0, 2)
-
-    def fetch(self, obs_dev, with_flags: bool = True):
-        e, k, n = self.envs, self.envs.k, self.envs.n
-        if not with_flags:  # after a reset: the whole current window, into both host histories
-            self.q, self.prev_reset = k - 1, None
-            w = obs_dev.transpose(0, 1)
-            for b in (0, 1):
-                self.H[b, :k, :, :F16_OBS_DIM].copy_(w, non_blocking=True)
-            if e.device.type == "cuda":
-                self.t.cuda.current_stream(e.device).synchronize()
-            return self._view(self.par), None, None, None
-        q = self.q + 1
-        if q >= self.Th:  # host restart: the last K-1 positions to the front of both histories
-            for b in (0, 1):
-                self.Hn[b, :k - 1] = self.Hn[b, q - k + 1:q]
-            q = k - 1
-        par = self.par ^ 1
-        new, other = e._layout.new_slots()  # position p of the current and of the other device history
-        self.H[par, q].copy_(new, non_blocking=True)
-        self.H[par ^ 1, q].copy_(other, non_blocking=True)
-        self.flags.copy_(e.step_flags, non_blocking=True)
-        self.t.cuda.current_stream(e.device).synchronize()
-        f = self.flags.numpy()
-        rew, term, trunc = f[:4 * n].view(np.float32), f[4 * n:5 * n], f[5 * n:6 * n]
-        Hc = self.Hn[par]
-        if k > 1 and self.prev_reset is not None and self.prev_reset.size:  # the kernel's FRESH fill
-            idx = self.prev_reset
-            Hc[q - k + 1:q, idx] = self.Hn[par ^ 1, q - 1, idx][None]
-        self.prev_reset = None
-        if self.autoreset:
-            idx = np.flatnonzero(term | trunc)
-            if idx.size:
-                if k > 1:  # lanes reset by this step: K-1 copies of their reset frame
-                    Hc[q - k + 1:q, idx] = Hc[q, idx][None]
-                self.prev_reset = idx
-        self.q, self.par = q, par
-        return self._view(par), rew, term, trunc
-
-    def done_rows(self, idx: np.ndarray):
-        """terminal obs (the other host history's window), episode return / length."""
-        e, t = self.envs, self.t
-        tobs = np.ascontiguousarray(self._view(self.par ^ 1)[idx])
-        i = t.as_tensor(idx, dtype=t.int64).to(e.device, non_blocking=True)
-        return tobs, e.ep_return.index_select(0, i).cpu().numpy(), e.ep_len.index_select(0, i).cpu().numpy()
-
-
-def _staging(envs, copy_obs: bool = False):
-    """The numpy-mode staging for a handle: the host window mirror for position-major windowed
-    handles (only the new slots cross PCIe), else whole-observation copies."""
-    lay = getattr(envs, "_layout", None)  # (a stand-in without a layout: whole-observation copies)
-    if isinstance(lay, _WindowLayout) and not lay.env_major and not copy_obs:
-        return _HostWindow(envs)
-    return _HostStaging(envs)
-
-
-class F16VecEnv(*_bases(SB3VecEnv)):
-    """Vectorised drop-in for ``DummyVecEnv([lambda: Monitor(gym.make("JSBSim-v0"))] * N)``.
-
-    Honours the SB3 VecEnv contract (base_vec_env.py:50-357): ``reset() -> obs``,
-    ``step_async/step_wait -> (obs, rews, dones, infos)``, auto-reset with
-    ``infos[i]["terminal_observation"]`` and ``infos[i]["TimeLimit.truncated"]``
-    (dummy_vec_env.py:56-73), Monitor's ``infos[i]["episode"] = {r, l, t}``
-    (monitor.py:96-109), ``seed()`` applied at the next reset (:292-309). When
-    stable_baselines3 is importable this class IS a ``VecEnv`` subclass, so
-    ``BaseAlgorithm._wrap_env`` (base_class.py:215) takes it as-is.
-
-    Numpy mode (default, what SB3 consumes): the handle steps in the windowed layout and the
-    host keeps a pinned mirror of its frame histories, so per step only the new frame slots
-    (2 x N x 64 B) and the packed rewards/flags cross PCIe, one stream sync (_HostWindow); the
-    obs returned is a strided (N, K, 15) numpy view of that mirror, valid until the step after
-    next (SB3 stores it one step later). ``copy_obs=True`` returns contiguous copies instead
-    (whole-observation D2H per step, _HostStaging), for consumers that keep observations
-    longer. Infos of lanes that did not finish share one read-only dict.
-    ``return_numpy=False`` keeps everything on the GPU (infos is then None: the caller reads the
-    ``last_step`` device tensors). ``envs=`` wraps an existing handle instead of creating one.
-    The handle it creates steps in the windowed observation layout in numpy mode and in the
-    contiguous one in device mode (``obs_layout=`` overrides)."""
-
-    metadata = {"render_modes": []}
-
-    def __init__(self, num_envs: int = 1, stack_k: int = 10, device=None, seed: int = 0,
-                 return_numpy: bool = True, env_id_base: int = 0, envs=None, copy_obs: bool = False, **kw):
-        if envs is None:
-            # numpy mode copies every observation to the host anyway, so the env steps in the
-            # windowed layout (no per-step stack rewrite: 16.9 vs 27.8 us at K = 10, 65 536 envs);
-            # device mode keeps dense (N, K, 15) buffers unless asked otherwise
-            kw.setdefault("obs_layout", "window" if return_numpy else "contiguous")
-            envs = F16Envs(num_envs, stack_k=stack_k, device=device, seed=seed, env_id_base=env_id_base, **kw)
-        self.envs = envs
-        n = self.envs.n
-        self.render_mode = None
-        self._attrs: dict = {}
-        obs_space, act_space = spaces.observation_space(self.envs.k), spaces.action_space()
-        if SB3VecEnv is not None:
-            SB3VecEnv.__init__(self, n, obs_space, act_space)  # base_vec_env.py:59-94
-        else:
-            self.num_envs = n
-            self.observation_space, self.action_space = obs_space, act_space
-            self.reset_infos: list = [{} for _ in range(n)]
-            self._seeds: list = [None for _ in range(n)]
-            self._options: list = [{} for _ in range(n)]
-        self.return_numpy = bool(return_numpy)
-        self.copy_obs = bool(copy_obs)
-        self._host = _staging(self.envs, self.copy_obs) if self.return_numpy else None
-        self._actions = None
-        self._t_start = time.time()
-        self.last_step: Optional[StepOut] = None
-
-    # -- VecEnv API -------------------------------------------------------------------------
-    def reset(self):
-        goals = None
-        if any(s is not None for s in self._seeds):
-            # seeded lanes follow the reference's numpy stream (jsbsim_gym.py:312-323); NaN rows
-            # draw the device goal, all in ONE reset (each lane's episode counter advances once)
-            goals = np.full((self.num_envs, 3), np.nan, np.float32)
-            for i, s in enumerate(self._seeds):
-                if s is not None:
-                    goals[i] = reference_goal(s)
-        obs = self.envs.reset(goals=goals)
-        self._seeds = [None for _ in range(self.num_envs)]
-        self._options = [{} for _ in range(self.num_envs)]
-        self.reset_infos = [{} for _ in range(self.num_envs)]
-        self._t_start = time.time()
-        if not self.return_numpy:
-            return obs
-        return self._host.fetch(obs, with_flags=False)[0]
-
-    def step_async(self, actions) -> None:
-        self._actions = actions
-
-    def step_wait(self):
-        if not self.return_numpy:
-            out = self.envs.step(self._actions)
-            self.last_step = out
-            return out.obs, out.rew, (out.terminated | out.truncated).bool(), None
-        out = self.envs.step(self._host.actions_to_device(self._actions))
-        self.last_step = out
-        obs, rew, term_u8, trunc_u8 = self._host.fetch(out.obs)
-        dones = (term_u8 | trunc_u8).astype(bool)
-        infos = [_NOT_DONE_INFO] * self.num_envs
-        idx = np.flatnonzero(dones)
-        if idx.size:
-            tobs, eret, elen = self._host.done_rows(idx)
-            t = round(time.time() - self._t_start, 6)
-            for j, i in enumerate(idx.tolist()):
-                info = {"TimeLimit.truncated": bool(trunc_u8[i] and not term_u8[i]),
-                        "terminal_observation": tobs[j],
-                        "episode": {"r": round(float(eret[j]), 6), "l": int(elen[j]), "t": t}}
-                if term_u8[i] & 2:  # NaN guard quarantine (nan_guard=True)
-                    info["nonfinite"] = True
-                infos[i] = info
-        if self.copy_obs:
-            obs = np.array(obs)
-        return obs, rew.copy(), dones, infos
-
-    def step(self, actions):
-        self.step_async(actions)
-        return self.step_wait()
-
-    def close(self) -> None:
-        self.envs.close()
-
-    def seed(self, seed: Optional[int] = None) -> Sequence[Optional[int]]:
-        if seed is None:
-            seed = int(np.random.randint(0, np.iinfo(np.uint32).max, dtype=np.uint32))
-        self._seeds = [seed + idx for idx in range(self.num_envs)]
-        return self._seeds
-
-    def set_options(self, options=None) -> None:
-        if options is None:
-            options = {}
-        self._options = deepcopy([options] * self.num_envs) if isinstance(options, dict) else deepcopy(options)
-
-    def _indices(self, indices):
-        if indices is None:
-            return range(self.num_envs)
-        if isinstance(indices, int):
-            return [indices]
-        return indices
-
-    # per-lane attributes of the reference env (jsbsim_gym.py:103-118), read from the device state
-    _LANE_ATTRS = ("current_step", "goal", "state")
-    _CONST_ATTRS = {"num_stacked_frames": "k", "max_episode_steps": None, "down_sample": None, "dg": None}
-
-    def get_attr(self, attr_name: str, indices=None) -> list:
-        idx = list(self._indices(indices))
-        if attr_name in self._attrs:
-            return [self._attrs[attr_name] for _ in idx]
-        if attr_name in ("render_mode", "observation_space", "action_space", "metadata"):
-            return [getattr(self, attr_name) for _ in idx]
-        if attr_name == "spec":
-            return [None for _ in idx]
-        c = self.envs.cfg
-        const = {"num_stacked_frames": self.envs.k, "max_episode_steps": int(c.max_steps),
-                 "down_sample": int(c.down_sample), "dg": float(c.dg_m)}
-        if attr_name in const:
-            return [const[attr_name] for _ in idx]
-        if attr_name in self._LANE_ATTRS:
-            from .abi import F16C_GOAL, F16C_STEP
-            if attr_name == "state":  # jsbsim_gym.py:181-193: newest frame's 12 state values
-                rows = self.envs.obs[:, -1, :12].index_select(0, self.envs.torch.as_tensor(idx, device=self.envs.device))
-                return list(rows.cpu().numpy())
-            st = self.envs.get_state().cpu().numpy()
-            if attr_name == "current_step":
-                return [int(st[i, F16C_STEP]) for i in idx]
-            return [st[i, F16C_GOAL:F16C_GOAL + 3].astype(np.float32) for i in idx]
-        raise AttributeError(attr_name)
-
-    def set_attr(self, attr_name: str, value: Any, indices=None) -> None:
-        self._attrs[attr_name] = value
-
-    def env_method(self, method_name: str, *method_args, indices=None, **method_kwargs) -> list:
-        """The single-env methods that make sense on device lanes: render (no renderer: None,
-        like an env without render_mode), get_wrapper_attr (gymnasium >= 1.0 attribute access),
-        reset (the indexed lanes, new goals from the device stream)."""
-        idx = list(self._indices(indices))
-        if method_name == "render":
-            return [None for _ in idx]
-        if method_name == "get_wrapper_attr":
-            return self.get_attr(method_args[0], idx)
-        if method_name == "reset":
-            mask = np.zeros(self.num_envs, np.uint8)
-            mask[idx] = 1
-            full = self.envs.reset(mask=mask)
-            if self._host is not None:  # the host mirror takes the new windows
-                self._host.fetch(full, with_flags=False)
-            obs = full[self.envs.torch.as_tensor(idx, device=self.envs.device)]
-            return [(o, {}) for o in obs.cpu().numpy()]
-        raise AttributeError("F16VecEnv lanes have no per-env method %r" % method_name)
-
-    def env_is_wrapped(self, wrapper_class, indices=None) -> list:
-        name = getattr(wrapper_class, "__name__", str(wrapper_class))
-        # Monitor / TimeLimit / PositionReward semantics are built into the kernel
-        wrapped = name in ("Monitor", "TimeLimit", "PositionReward")
-        return [wrapped for _ in self._indices(indices)]
-
-    def has_attr(self, attr_name: str) -> bool:
-        try:
-            self.get_attr(attr_name, 0)
-            return True
-        except AttributeError:
-            return False
-
-    def get_images(self):
-        raise NotImplementedError("rendering is out of scope (SURVEY.md component #9)")
-
-    def render(self, mode: Optional[str] = None):
-        return None
-
-    @property
-    def unwrapped(self):
-        return self
-
-
-class F16GymVectorEnv(*_bases(GymVectorEnv)):
-    """gymnasium.vector.VectorEnv surface over the same kernel (the north star's "Gymnasium
-    VectorEnv step()/reset()"), for gymnasium-native learners; a VectorEnv subclass when
-    gymnasium is importable (registered as "JSBSim-v0"'s vector entry point,
-    f16_jsb_amd/__init__.py). Autoreset mode SAME_STEP -- what the kernel does: a lane that
-    terminates or truncates returns its reset observation in the same step, and
-
-      infos["final_obs"] / infos["_final_obs"]   final (K,15) observation / mask
-      infos["episode"] = {"r", "l", "t"}, infos["_episode"]   (RecordEpisodeStatistics keys)
-
-    are filled for the finished lanes (gymnasium's vector-info convention: a value array plus a
-    "_key" boolean mask). ``reset(seed=s)`` seeds env i with s + i (the reference's
-    default_rng(seed) goal, jsbsim_gym.py:312-323). Single-env semantics are jsbsim_gym.py's
-    JSBSimEnv wrapped in TimeLimit(1200) and PositionReward(1e-2) (jsbsim_gym.py:537-545).
-
-    Numpy mode returns observations as strided views of a pinned host mirror of the windowed
-    handle's frame histories (_HostWindow): an obs array stays valid until the step after next
-    (the next step leaves it intact, the one after overwrites it). A consumer that keeps
-    observations longer passes ``copy_obs=True`` (contiguous copies; whole-observation
-    device-to-host copies per step). ``infos["final_obs"]`` is always a copy."""
-
-    metadata = {"autoreset_mode": "SameStep", "render_modes": []}
-
-    def __init__(self, num_envs: int = 1, stack_k: int = 10, device=None, seed: int = 0,
-                 return_numpy: bool = True, envs=None, copy_obs: bool = False, **kw):
-        if envs is None:  # as F16VecEnv: the windowed layout when observations go to the host
-            kw.setdefault("obs_layout", "window" if return_numpy else "contiguous")
-            envs = F16Envs(num_envs, stack_k=stack_k, device=device, seed=seed, **kw)
-        self.envs = envs
-        self.num_envs = self.envs.n
-        self.single_observation_space = spaces.observation_space(self.envs.k)
-        self.single_action_space = spaces.action_space()
-        self.observation_space = spaces.batch_space(self.single_observation_space, self.num_envs)
-        self.action_space = spaces.batch_space(self.single_action_space, self.num_envs)
-        self.render_mode = None
-        self.spec = None
-        self.closed = False
-        self.return_numpy = bool(return_numpy)
-        self.copy_obs = bool(copy_obs)
-        self._host = _staging(self.envs, self.copy_obs) if self.return_numpy else None
-        self._t_start = time.time()
-
-    def reset(self, *, seed=None, options=None):
-        goals = None
-        if seed is not None:
-            seeds = [seed + i for i in range(self.num_envs)] if isinstance(seed, int) else list(seed)
-            if len(seeds) != self.num_envs:
-                raise ValueError("need one seed per env")
-            goals = np.full((self.num_envs, 3), np.nan, np.float32)  # NaN rows: device goal
-            for i, s in enumerate(seeds):
-                if s is not None:
-                    goals[i] = reference_goal(s)
-        obs = self.envs.reset(goals=goals)
-        self._t_start = time.time()
-        if not self.return_numpy:
-            return obs, {}
-        o = self._host.fetch(obs, with_flags=False)[0]
-        return (np.array(o) if self.copy_obs else o), {}
-
-    def step(self, actions):
-        if not self.return_numpy:
-            out = self.envs.step(actions)
-            term, trunc = out.terminated.bool(), out.truncated.bool()
-            done = term | trunc
-            infos = {}
-            if bool(done.any()):
-                t = round(time.time() - self._t_start, 6)
-                infos["final_obs"] = out.terminal_obs.clone()
-                infos["_final_obs"] = done
-                infos["episode"] = {"r": t_where(done, out.ep_return, 0.0), "l": t_where(done, out.ep_len, 0),
-                                    "t": t_where(done, t, 0.0)}
-                infos["_episode"] = done
-            return out.obs, out.rew, term, trunc, infos
-        out = self.envs.step(self._host.actions_to_device(actions))
-        obs, rew, term_u8, trunc_u8 = self._host.fetch(out.obs)
-        term, trunc = term_u8.astype(bool), trunc_u8.astype(bool)
-        done = term | trunc
-        infos = {}
-        idx = np.flatnonzero(done)
-        if idx.size:
-            t = round(time.time() - self._t_start, 6)
-            tobs, eret, elen = self._host.done_rows(idx)
-            final = np.zeros_like(obs)
-            final[idx] = tobs
-            r = np.zeros(self.num_envs)
-            r[idx] = np.round(eret, 6)
-            ln = np.zeros(self.num_envs, np.int32)
-            ln[idx] = elen
-            infos["final_obs"] = final
-            infos["_final_obs"] = done
-            infos["episode"] = {"r": r, "l": ln, "t": np.where(done, t, 0.0)}
-            infos["_episode"] = done
-        if self.copy_obs:
-            obs = np.array(obs)
-        return obs, rew.copy(), term, trunc, infos
-
-    def close(self, **kwargs):
-        if not self.closed:
-            self.envs.close()
-            self.closed = True
-
-    def render(self):
-        return None
-
-    @property
-    def unwrapped(self):
-        return self
-
-
-def t_where(mask, x, other):
-    import torch
-    if not isinstance(x, torch.Tensor):
-        x = torch.full(mask.shape, float(x), device=mask.device)
-    return torch.where(mask, x, torch.as_tensor(other, dtype=x.dtype, device=x.device))
-
-
-class F16GymEnv(*_bases(GymEnv)):
-    """ONE env with the single-env gymnasium surface of ``gym.make("JSBSim-v0")``
-    (jsbsim_gym.py:537-545: JSBSimEnv wrapped in PositionReward(1e-2), TimeLimit(1200)) over a
-    one-lane handle: ``reset(seed, options) -> (obs (K,15), {})`` with the default_rng(seed)
-    goal of jsbsim_gym.py:312-323 (seed None: the device goal stream), ``step(action) ->
-    (obs, reward, terminated, truncated, {})``, no auto-reset (the caller resets, as with the
-    reference). A gymnasium.Env subclass when gymnasium is importable; the entry point
-    "JSBSim-v0" is registered to (f16_jsb_amd/__init__.py), so an unchanged train.py gets a
-    GPU-backed env from gym.make -- one env, SB3 then wraps it in Monitor + DummyVecEnv as it
-    does the reference's. For throughput use F16VecEnv."""
-
-    metadata = {"render_modes": []}
-
-    def __init__(self, stack_k: int = 10, device=None, seed: int = 0, envs=None, **kw):
-        self.envs = envs if envs is not None else F16Envs(1, stack_k=stack_k, device=device, seed=seed,
-                                                          autoreset=False, **kw)
-        self.observation_space = spaces.observation_space(self.envs.k)
-        self.action_space = spaces.action_space()
-        self.render_mode = None
-        self._host = _HostStaging(self.envs, ring=2)
-
-    def reset(self, *, seed=None, options=None):
-        if GymEnv is not None:
-            GymEnv.reset(self, seed=seed)  # gymnasium's np_random seeding (jsbsim_gym.py:302)
-        goals = None if seed is None else reference_goal(seed)[None]
-        obs = self.envs.reset(goals=goals)
-        return self._host.fetch(obs, with_flags=False)[0][0].copy(), {}
-
-    def step(self, action):
-        out = self.envs.step(self._host.actions_to_device(np.asarray(action, np.float32).reshape(1, 4)))
-        obs, rew, term, trunc = self._host.fetch(out.obs)
-        return obs[0].copy(), float(rew[0]), bool(term[0]), bool(trunc[0]), {}
-
-    def render(self):
-        return None
-
-    def close(self):
-        self.envs.close()
-
-    @property
-    def unwrapped(self):
-        return self
-
-
-def make_gym_env(**kw) -> F16GymEnv:
-    """gymnasium entry point of "JSBSim-v0" (jsbsim_gym.py:537-545 wrap_jsbsim counterpart)."""
-    kw.pop("root", None)  # JSBSimEnv(root=...) names a JSBSim data directory: nothing to load here
-    return F16GymEnv(**kw)
-
-
-def make_gym_vector_env(num_envs: int = 1, **kw) -> F16GymVectorEnv:
-    """gymnasium vector entry point of "JSBSim-v0" (gymnasium.make_vec)."""
-    kw.pop("root", None)
-    return F16GymVectorEnv(num_envs=num_envs, **kw)
+def __getattr__(name):  # the facades' old import path (lazy, as in __init__.py); nothing else is forwarded
+    if name in ("F16VecEnv", "F16GymVectorEnv", "F16GymEnv"):
+        from . import vec_env
+        return getattr(vec_env, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,14 +1,18 @@
 """A CPU stand-in for F16Envs (TEST INFRASTRUCTURE): the same buffers and call surface, with
 trivial deterministic "dynamics", so the host logic of the VecEnv / gymnasium facades
-(f16_jsb_amd/env.py) can be tested without a GPU. Lane i terminates at step 2 + i % 3 when i is
-even and truncates at max_steps when odd; frame = [lane, step, episode, act0..3, 0.., goal]."""
+(f16_jsb_amd/vec_env.py) and of their host staging (host_staging.py) can be tested without a GPU.
+Lane i terminates at step 2 + i % 3 when i is even and truncates at max_steps when odd; frame =
+[lane, step, episode, act0..3, 0.., goal]. FakeEnvs has no layout: the facades copy its whole
+observations. FakeWindowEnvs also hands out the two new frame slots of a step, as a windowed
+handle does, so the facades mirror it slot by slot (_HostWindow)."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from f16_jsb_amd.abi import F16C_EP_COUNT, F16C_GOAL, F16C_N, F16C_STEP, config_default
-from f16_jsb_amd.env import StepOut
+from f16_jsb_amd.buffers import split_step_flags, step_flags_bytes
+from f16_jsb_amd.layouts import StepOut
 
 
 class FakeEnvs:
@@ -16,11 +20,8 @@ class FakeEnvs:
         self.torch, self.n, self.k = torch, n, k
         self.device = torch.device("cpu")
         self.cfg = config_default(n_envs=n, stack_k=k, max_steps=max_steps)
-        nb = (6 * n + 15) // 16 * 16
-        self.step_flags = torch.zeros(nb, dtype=torch.uint8)
-        self.rew = self.step_flags[:4 * n].view(torch.float32)
-        self.term = self.step_flags[4 * n:5 * n]
-        self.trunc = self.step_flags[5 * n:6 * n]
+        self.step_flags = torch.zeros(step_flags_bytes(n), dtype=torch.uint8)
+        self.rew, self.term, self.trunc = split_step_flags(self.step_flags, n, torch.float32)
         self.terminal_obs = torch.zeros((n, k, 15))
         self.ep_return = torch.zeros(n, dtype=torch.float64)
         self.ep_len = torch.zeros(n, dtype=torch.int32)
@@ -88,3 +89,20 @@ class FakeEnvs:
 
     def close(self):
         self.closed = True
+
+
+class FakeWindowEnvs(FakeEnvs):
+    """FakeEnvs with the mirror surface of a position-major windowed handle."""
+    mirrors_by_slot = True
+
+    def new_frame_slots(self):
+        """The last step's two (N, 16) slot blocks by the windowed step kernel's rule: the current
+        history gets the new frame of the returned observation (a finished lane's reset frame), the
+        other history the frame that ended the episode for finished lanes and the same new frame for
+        the rest; the 16th float of a slot is 0."""
+        done = (self.term | self.trunc).bool()
+        cur = torch.zeros((self.n, 16))
+        cur[:, :15] = self._obs[:, -1]
+        other = cur.clone()
+        other[done, :15] = self.terminal_obs[done, -1]
+        return cur, other

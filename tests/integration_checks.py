@@ -13,15 +13,20 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def check_vecenv_contract():
+def check_vecenv_contract(fake_cls=None, staging=None, keep=2):
+    """fake_cls: the stand-in handle (default FakeEnvs); staging: the class the chooser must pick for
+    it; keep: the further steps an observation must outlast (2: the ring of 3 of whole copies; the
+    host window mirror promises 1, the device layout's own guarantee)."""
     import f16_jsb_amd
-    from f16_jsb_amd.env import F16VecEnv, _ReadOnlyInfo, reference_goal
+    from f16_jsb_amd.env import reference_goal
+    from f16_jsb_amd.vec_env import F16VecEnv, _ReadOnlyInfo
     from fake_envs import FakeEnvs
 
     n, k = 6, 4
-    fake = FakeEnvs(n, k, max_steps=6)
+    fake = (fake_cls or FakeEnvs)(n, k, max_steps=6)
     venv = f16_jsb_amd.make("JSBSim-v0", envs=fake)
     assert isinstance(venv, F16VecEnv) and venv.num_envs == n
+    assert staging is None or type(venv._host) is staging
     assert venv.observation_space.shape == (k, 15) and venv.action_space.shape == (4,)
     # seed() applies at the next reset (base_vec_env.py:292-309); mixed seeded / unseeded lanes in
     # ONE reset: every lane's episode counter advances exactly once (ADVICE r01)
@@ -69,8 +74,8 @@ def check_vecenv_contract():
             except TypeError:
                 pass
         # an obs array returned two steps ago is still intact (pinned ring of 3)
-        if len(kept) >= 3:
-            a, snap = kept[-3]
+        if len(kept) >= keep + 1:
+            a, snap = kept[-keep - 1]
             np.testing.assert_array_equal(a, snap)
     assert ended >= n
     # attributes of the reference env (jsbsim_gym.py:103-118) per lane
@@ -85,14 +90,15 @@ def check_vecenv_contract():
     assert fake.closed
 
 
-def check_gym_vector_contract():
+def check_gym_vector_contract(fake_cls=None, staging=None):
     import f16_jsb_amd
     from f16_jsb_amd.env import reference_goal
     from fake_envs import FakeEnvs
 
     n = 5
-    fake = FakeEnvs(n, 3, max_steps=4)
+    fake = (fake_cls or FakeEnvs)(n, 3, max_steps=4)
     env = f16_jsb_amd.make_vec("JSBSim-v0", num_envs=n, envs=fake)
+    assert staging is None or type(env._host) is staging
     obs, info = env.reset(seed=7)
     assert info == {} and obs.shape == (n, 3, 15)
     for i in range(n):
@@ -128,8 +134,8 @@ def check_registration_and_subclassing():
     assert issubclass(E.F16GymVectorEnv, gymnasium.vector.VectorEnv)
     assert issubclass(E.F16GymEnv, gymnasium.Env)
     spec = gymnasium.registry["JSBSim-v0"]
-    assert spec.entry_point == "f16_jsb_amd.env:make_gym_env" and spec.max_episode_steps == 1200
-    assert spec.vector_entry_point == "f16_jsb_amd.env:make_gym_vector_env"
+    assert spec.entry_point == "f16_jsb_amd.vec_env:make_gym_env" and spec.max_episode_steps == 1200
+    assert spec.vector_entry_point == "f16_jsb_amd.vec_env:make_gym_vector_env"
     assert f16_jsb_amd.register_gymnasium() is False  # idempotent
     venv = f16_jsb_amd.make("JSBSim-v0", envs=FakeEnvs(4, 4))
     assert isinstance(venv, VecEnv) and wrap_env(venv) is venv

@@ -428,7 +428,8 @@ def test_vecenv_host_window_matches_full_copy(torch_mod, k, cfg5):
     observations and episode statistics bit-identical at every step, through short episodes
     (auto-resets every few steps, cfg5's in-step resets), device window restarts (history 16)
     and host ring restarts (Th = 2K + 3); the obs returned one step earlier is unchanged."""
-    from f16_jsb_amd.env import F16VecEnv, _HostStaging, _HostWindow
+    from f16_jsb_amd.host_staging import _HostStaging, _HostWindow
+    from f16_jsb_amd.vec_env import F16VecEnv
     n = 700
     kw = dict(num_envs=n, stack_k=k, seed=3, max_steps=7, history=max(16, 2 * k), cfg5=cfg5)
     a = F16VecEnv(**kw)
@@ -454,6 +455,46 @@ def test_vecenv_host_window_matches_full_copy(torch_mod, k, cfg5):
         if prev is not None:
             np.testing.assert_array_equal(prev[0], prev[1], err_msg="previous obs changed @%d" % t)
         prev = (oa, oa.copy())
+    assert ended > n
+    a.close()
+    b.close()
+
+
+@pytest.mark.parametrize("k", [1, 4])
+def test_gym_vector_host_window_matches_full_copy(torch_mod, k):
+    """F16GymVectorEnv numpy mode with the host window mirror against whole-observation copies
+    (copy_obs=True) on identical handles, as the test above does for F16VecEnv: every output of every
+    step bit-identical, through auto-resets every few steps, device window restarts (history 16) and
+    host ring restarts (Th = 2K + 3); one full 256-lane block and one lane; K = 1 has no fills at all."""
+    from f16_jsb_amd.host_staging import _HostStaging, _HostWindow
+    from f16_jsb_amd.vec_env import F16GymVectorEnv
+    n = 257
+    kw = dict(num_envs=n, stack_k=k, seed=3, max_steps=7, history=16)
+    a = F16GymVectorEnv(**kw)
+    assert type(a._host) is _HostWindow
+    a._host = _HostWindow(a.envs, th=2 * k + 3)
+    b = F16GymVectorEnv(copy_obs=True, **kw)
+    assert type(b._host) is _HostStaging
+    np.testing.assert_array_equal(a.reset(seed=11)[0], b.reset(seed=11)[0])
+    rng = np.random.default_rng(1)
+    prev = None
+    ended = 0
+    for t in range(40):
+        act = rng.uniform([-1, -1, -1, 0], [1, 1, 1, 1], (n, 4)).astype(np.float32)
+        ra, rb = a.step(act), b.step(act)
+        for x, y, what in zip(ra[:4], rb[:4], ("obs", "rew", "term", "trunc")):
+            np.testing.assert_array_equal(x, y, err_msg="%s @%d" % (what, t))
+        ia, ib = ra[4], rb[4]
+        assert set(ia) == set(ib)
+        if ib:
+            np.testing.assert_array_equal(ia["final_obs"], ib["final_obs"], err_msg="final_obs @%d" % t)
+            np.testing.assert_array_equal(ia["_final_obs"], ib["_final_obs"])
+            np.testing.assert_array_equal(ia["episode"]["r"], ib["episode"]["r"])
+            np.testing.assert_array_equal(ia["episode"]["l"], ib["episode"]["l"])
+            ended += int(ib["_final_obs"].sum())
+        if prev is not None:
+            np.testing.assert_array_equal(prev[0], prev[1], err_msg="previous obs changed @%d" % t)
+        prev = (ra[0], ra[0].copy())
     assert ended > n
     a.close()
     b.close()

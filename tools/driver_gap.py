@@ -39,7 +39,7 @@ def main():
     import numpy as np
     import torch
     from bench import spread_phases
-    from f16_jsb_amd.env import F16VecEnv
+    from f16_jsb_amd.vec_env import F16VecEnv
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
